@@ -9,7 +9,7 @@ Everything runs through the product's drop-in surface (surfel_trainer.Trainer ov
 include/surfel_train.h kernels); inputs (parameters, target images, cameras) are resident in HBM before the timed region.
 N > 1: view-parallel — every rank trains on a different view of the same replicated surfel set per step (weak scaling).
 
-Prints ONE JSON line on rank 0.  `value` = whole-job training iterations (views) per second.
+Prints ONE JSON line on rank 0 (result_line: at most LINE_MAX characters).  `value` = whole-job training iterations (views) per second.
 Side legs at N = 1: rasterizer-only fwd+bwd, forward-only Msplats/s @1080p (BASELINE metric), CPU baseline (oracle port).
 """
 import argparse
@@ -130,6 +130,65 @@ def step_roofline(kernels_ms, ms_per_step, workload, P, V, R, Rs, W, H):
     return out
 
 
+# ---- the printed line: the headline and its roofline in full, every side object cut to its top-level numbers (the whole object goes
+# to --detail-json).  Readers of the line keep only a bounded tail of stdout: a 21 KB line was not read back at all.
+LINE_MAX = 6144
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                 "config", "loss_first", "loss_last", "train_Msplats_per_s", "world_size_seen", "backend", "roofline", "step_roofline", "cpu_baseline")
+ROOFLINE_DETAIL = ("all_kernels_GBps", "window", "traffic_source")
+
+
+def _numbers(obj):
+    """A side object's top-level numbers (or its error): what the one-line result keeps of it."""
+    if not isinstance(obj, dict):
+        return obj if isinstance(obj, (int, float, bool)) else None
+    if "error" in obj:
+        return {"error": str(obj["error"])[:200]}
+    return {k: v for k, v in obj.items() if isinstance(v, (int, float, bool))}
+
+
+def result_line(out):
+    """The one JSON line bench.py prints: at most LINE_MAX characters, every HEADLINE_KEYS entry of `out` present."""
+    line = {k: out[k] for k in HEADLINE_KEYS if k in out}
+    if isinstance(line.get("config"), dict):
+        line["config"] = {k: v for k, v in line["config"].items() if k != "trained_state"}
+    if isinstance(line.get("roofline"), dict):
+        line["roofline"] = {k: v for k, v in line["roofline"].items() if k not in ROOFLINE_DETAIL}
+    side = [k for k in out if k not in HEADLINE_KEYS]
+    for k in side:
+        line[k] = {n: _numbers(v) for n, v in out[k].items()} if k == "legs" and isinstance(out[k], dict) else _numbers(out[k])
+    for k in sorted(side, key=lambda k: -len(json.dumps(line[k]))):      # still too long: the largest side objects go first
+        if len(json.dumps(line)) <= LINE_MAX:
+            break
+        del line[k]
+    return json.dumps(line)
+
+
+def dump_outputs(tr, out_dir, n_sample=32768, seed=20261015):
+    """--dump-outputs: what the last timed step hands its caller, as .npy files in out_dir (float32, indices float64).  Trainer.step()
+    returns nothing: it leaves the step's loss terms and radii in tr.last and the model updated in place (parameters, Adam moments,
+    densification statistics; the gradient store is zeroed by the optimiser step).  Per-surfel arrays are cut to a fixed, seeded sample
+    of n_sample surfels (~24 MB in all); the same arguments give the same sample."""
+    import numpy as np
+    import torch
+    from surfel_model import _views
+    m = tr.model
+    P = int(m.P)
+    idx = np.sort(np.random.default_rng(seed).choice(P, size=min(P, n_sample), replace=False))
+    sel = torch.from_numpy(idx).to(m.theta.device)
+
+    def rows(flat):      # [P * FLOATS] section-major store -> [n, FLOATS] rows of the sample, sections in surfel_model.SECTIONS order
+        return torch.cat([v[sel] for v in _views(flat, P).values()], dim=1)
+
+    arrays = {"loss_terms": tr.last["scalars"].reshape(-1), "surfel_index": idx.astype(np.float64), "radii": tr.last["radii"].reshape(-1)[sel],
+              "params": rows(m.theta), "adam_m": rows(m.m), "adam_v": rows(m.v),
+              "xyz_gradient_accum": m.xyz_gradient_accum.reshape(-1)[sel], "denom": m.denom.reshape(-1)[sel], "max_radii2D": m.max_radii2D.reshape(-1)[sel]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def _respawn(n):
     """Re-execute this command line under torch.distributed.run with n ranks on this node; returns its exit code."""
     import socket
@@ -190,6 +249,11 @@ def main():
                          "per iteration across the GPUs (strong scaling; BASELINE config 5: --workload C5)")
     ap.add_argument("--rehearse-spawn", action="store_true",
                     help="only exercise the launch path: spawn / rendezvous (gloo, no GPU needed), one all-reduce, print n_gpus and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss terms, radii, and for a fixed sample of surfels the "
+                         "updated parameters, Adam moments and densification statistics) as DIR/<name>.npy")
+    ap.add_argument("--detail-json", metavar="PATH", default=None,
+                    help="also write the full result object (every side leg in full) to PATH; stdout gets the compact line")
     args = ap.parse_args()
 
     # ---- launch contract: `python bench.py --gpus N` run DIRECTLY must time N ranks.  Without a torch.distributed.run
@@ -284,6 +348,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     ms1 = torch.cuda.memory_stats(dev)
+    if args.dump_outputs and rank == 0:      # (before the census below steps the model again)
+        dump_outputs(tr, args.dump_outputs)
     # (diagnostics of the window, nothing is re-timed: device allocations inside it and the host's own time per step)
     timed_window = {"device_allocs": int(ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0)),
                     "device_frees": int(ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0)),
@@ -486,7 +552,10 @@ def main():
             out["cpu_baseline_dense_torch_C1"] = {"error": repr(e)}
 
     if rank == 0:
-        print(json.dumps(out))
+        if args.detail_json:
+            with open(args.detail_json, "w") as f:
+                json.dump(out, f)
+        print(result_line(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

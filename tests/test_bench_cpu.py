@@ -5,6 +5,7 @@ import os
 import socket
 import subprocess
 import sys
+import types
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(REPO, "bench.py")
@@ -43,3 +44,48 @@ def test_world_size_mismatch_fails_loudly():
     env = _env(); env.update(WORLD_SIZE="4", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse-spawn"], capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE=4" in (r.stderr + r.stdout)
+
+
+def test_result_line_is_compact_and_keeps_the_headline():
+    """The printed line of a full N = 1 run (every side leg on, profiles/r06_bench_n1_final.json: 21.7 KB as one object) fits in
+    bench.LINE_MAX and keeps the headline, its roofline and the CPU baseline; side legs keep their numbers."""
+    sys.path.insert(0, REPO)
+    import bench
+    with open(os.path.join(REPO, "profiles", "r06_bench_n1_final.json")) as f:
+        full = json.loads(f.read().strip().splitlines()[-1])
+    line = bench.result_line(full)
+    assert "\n" not in line and len(line) <= bench.LINE_MAX, len(line)
+    j = json.loads(line)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "dtype", "config", "roofline", "step_roofline", "cpu_baseline"):
+        assert j[k] == full[k] or k in ("config", "roofline"), k
+    assert j["config"]["workload"] == full["config"]["workload"] and j["roofline"]["all_kernels_ms"] == full["roofline"]["all_kernels_ms"]
+    assert j["legs"]["C2"]["ms_per_step"] == full["legs"]["C2"]["ms_per_step"]
+
+
+def test_dump_outputs_sample_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs on a stand-in trainer (host tensors in the model's layout): float32 / float64 files, the same sample every
+    time, per-surfel rows matching the store, well under 64 MB for a garden-sized model."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    from surfel_model import FLOATS, SECTIONS, _views
+    P = 2_200_000
+    g = torch.Generator().manual_seed(0)
+    m = types.SimpleNamespace(P=P, theta=torch.rand(P * FLOATS, generator=g), m=torch.rand(P * FLOATS, generator=g),
+                              v=torch.rand(P * FLOATS, generator=g), xyz_gradient_accum=torch.rand(P, 1, generator=g),
+                              denom=torch.rand(P, 1, generator=g), max_radii2D=torch.rand(P, generator=g))
+    tr = types.SimpleNamespace(model=m, last=dict(scalars=torch.rand(6, generator=g), radii=torch.randint(0, 9, (P,), dtype=torch.int32)))
+    bench.dump_outputs(tr, str(tmp_path / "a"))
+    bench.dump_outputs(tr, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "params.npy" in names and "loss_terms.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    idx = np.load(tmp_path / "a" / "surfel_index.npy").astype(np.int64)
+    params = np.load(tmp_path / "a" / "params.npy")
+    xyz = _views(m.theta, P)["xyz"].numpy()
+    assert params.shape == (len(idx), FLOATS) and SECTIONS[0][0] == "xyz" and np.array_equal(params[:, :3], xyz[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "radii.npy"), tr.last["radii"].numpy()[idx].astype(np.float32))
