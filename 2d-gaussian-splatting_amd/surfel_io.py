@@ -56,3 +56,92 @@ def read_ply(path):
         dt = np.dtype([(n, order + t) for n, t in props])
         rec = np.frombuffer(f.read(count * dt.itemsize), dtype=dt, count=count)
         return {n: np.ascontiguousarray(rec[n]) for n, _ in props}
+
+
+# ------------------------------------------------------------------------------------------------ triangle meshes and cameras
+def write_triangle_mesh(path, mesh):
+    """Binary little-endian PLY of a mesh with .vertices [V,3], .vertex_colors [V,3] (0..1) and .triangles [F,3] (numpy arrays or
+    tensors): float x,y,z, uchar red,green,blue per vertex and `list uchar int vertex_indices` per face."""
+    def host(x):
+        return np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x)
+    v = host(mesh.vertices).astype("<f4").reshape(-1, 3)
+    c = host(mesh.vertex_colors).reshape(-1, 3)
+    f = host(mesh.triangles).astype("<i4").reshape(-1, 3)
+    vrec = np.empty(v.shape[0], dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    vrec["xyz"] = v
+    vrec["rgb"] = np.round(np.clip(c, 0.0, 1.0) * 255.0).astype(np.uint8) if c.size else c.astype(np.uint8)
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", 3)])
+    frec["n"] = 3
+    frec["idx"] = f
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0], "property float x", "property float y",
+              "property float z", "property uchar red", "property uchar green", "property uchar blue", "element face %d" % f.shape[0],
+              "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def read_triangle_mesh(path):
+    """(vertices [V,3] float32, triangles [F,3] int32, vertex_colors [V,3] float32 in 0..1) of a binary little-endian PLY with
+    float x,y,z (+ optional uchar red,green,blue) vertices and triangle faces (`list uchar int|uint vertex_indices`)."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError("%s is not a PLY file" % path)
+        elements, cur = [], None
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError("%s: truncated PLY header" % path)
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format" and tok[1] != "binary_little_endian":
+                raise ValueError("%s: only binary_little_endian meshes are supported" % path)
+            if tok[0] == "element":
+                cur = [tok[1], int(tok[2]), []]
+                elements.append(cur)
+            elif tok[0] == "property":
+                cur[2].append(tuple(tok[1:]))
+            elif tok[0] == "end_header":
+                break
+        verts = tris = cols = None
+        for name, count, props in elements:
+            if name == "vertex":
+                dt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
+                rec = np.frombuffer(fh.read(count * dt.itemsize), dtype=dt, count=count)
+                verts = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
+                if "red" in dt.names:
+                    cols = np.stack([rec["red"], rec["green"], rec["blue"]], 1).astype(np.float32) / 255.0
+                else:
+                    cols = np.zeros((count, 3), np.float32)
+            elif name == "face":
+                if len(props) != 1 or props[0][0] != "list":
+                    raise ValueError("%s: faces must hold one list property" % path)
+                dt = np.dtype([("n", _PLY_TYPES[props[0][1]]), ("idx", "<" + _PLY_TYPES[props[0][2]], 3)])
+                rec = np.frombuffer(fh.read(count * dt.itemsize), dtype=dt, count=count)
+                if count and np.any(rec["n"] != 3):
+                    raise ValueError("%s: only triangle faces are supported" % path)
+                tris = rec["idx"].astype(np.int32).reshape(-1, 3)
+            else:
+                raise ValueError("%s: unexpected element %s" % (path, name))
+    if tris is None:
+        tris = np.zeros((0, 3), np.int32)
+    return verts, tris, cols
+
+
+def read_cameras_json(path, device="cuda"):
+    """surfel_render.Camera list from the reference's cameras.json (utils/camera_utils.py:64-84 writes it: `position` and `rotation` are
+    the camera-to-world translation and rotation, fx / fy in pixels).  The cameras carry a black placeholder image of their size."""
+    import json
+    import torch
+    from surfel_render import Camera
+    cams = []
+    for e in json.load(open(path)):
+        R = np.asarray(e["rotation"], np.float64)           # C2W rotation = the reference's Camera.R
+        T = -R.T @ np.asarray(e["position"], np.float64)    # W2C translation
+        W, H = int(e["width"]), int(e["height"])
+        fovx, fovy = 2 * np.arctan(W / (2 * float(e["fx"]))), 2 * np.arctan(H / (2 * float(e["fy"])))
+        cams.append(Camera(colmap_id=e["id"], R=R, T=T, FoVx=fovx, FoVy=fovy, image=torch.zeros(3, H, W), image_name=e.get("img_name", ""),
+                           uid=e["id"], data_device=device))
+    return cams

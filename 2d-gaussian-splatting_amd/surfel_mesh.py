@@ -1,0 +1,354 @@
+"""Bounded TSDF mesh extraction on MI355X — the reference's `GaussianExtractor` bounded path and `post_process_mesh`
+(utils/mesh_utils.py:22-181) and the mesh step of render.py:86-106, without Open3D.
+
+The fusion, marching cubes and the connected-component filter are HIP kernels of libsurfel_hip.so (include/surfel_mesh.h); the
+rules they follow are written down in MESH.md.  Maps stay on the device; only counts cross to the host.
+
+    python 2d-gaussian-splatting_amd/surfel_mesh.py -m MODEL_DIR [--iteration N] [--mesh_res 1024] ...
+"""
+import argparse
+import ctypes as C
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+import surfel_native as _n
+
+_n.load()
+
+
+def _check(rc, what):
+    if rc < 0:
+        raise RuntimeError("%s failed (%d): %s" % (what, rc, _n.last_error()))
+    return rc
+
+
+class MeshLimitError(RuntimeError):
+    """SURFEL_E_LIMIT: the volume would exceed the byte budget (raise the budget or the voxel size)."""
+
+
+class TriangleMesh:
+    """vertices [V,3] float32, triangles [F,3] int32, vertex_colors [V,3] float32 in 0..1 — Open3D's attribute names; torch
+    tensors (on the device after extraction)."""
+
+    def __init__(self, vertices, triangles, vertex_colors):
+        self.vertices, self.triangles, self.vertex_colors = vertices, triangles, vertex_colors
+
+    def numpy(self):
+        return TriangleMesh(*(np.asarray(x.cpu().numpy() if torch.is_tensor(x) else x) for x in (self.vertices, self.triangles, self.vertex_colors)))
+
+
+# ------------------------------------------------------------------------------------------------ cameras
+def camera_intrinsics(cam):
+    """(fx, fy, cx, cy) as utils/mesh_utils.py:43-68: (projection_matrix @ ndc2pix)[:3,:3].T with cx = (W-1)/2, cy = (H-1)/2."""
+    W, H = int(cam.image_width), int(cam.image_height)
+    ndc2pix = np.array([[W / 2, 0, 0, (W - 1) / 2], [0, H / 2, 0, (H - 1) / 2], [0, 0, 0, 1]], np.float64).T
+    intr = (np.asarray(cam.projection_matrix.detach().cpu().numpy(), np.float64) @ ndc2pix)[:3, :3].T
+    return float(intr[0, 0]), float(intr[1, 1]), float(intr[0, 2]), float(intr[1, 2])
+
+
+def camera_block(cam):
+    """The 16-float camera of include/surfel_mesh.h: extrinsic = world_view_transform.T (rows 0..2), then fx, fy, cx, cy."""
+    ext = np.asarray(cam.world_view_transform.detach().cpu().numpy(), np.float64).T
+    out = np.zeros(16, np.float32)
+    out[:12] = ext[:3, :4].reshape(-1)
+    out[12:] = camera_intrinsics(cam)
+    return out
+
+
+def bounding_sphere(c2ws):
+    """(center, radius) from camera-to-world matrices [N,4,4]: the point nearest (least squares) to every optical axis — the line
+    through the camera centre along its viewing direction, the camera's +z (the reference's poses flip y and z and look along -z,
+    the same line) — and its smallest distance to a camera centre."""
+    c2ws = np.asarray(c2ws, np.float64)
+    o, d = c2ws[:, :3, 3], c2ws[:, :3, 2]
+    d = d / np.linalg.norm(d, axis=1, keepdims=True)
+    P = np.eye(3)[None] - d[:, :, None] * d[:, None, :]       # projector onto the plane normal to each axis
+    center = np.linalg.solve(P.sum(0), np.einsum("nij,nj->i", P, o))
+    return center, float(np.linalg.norm(o - center, axis=1).min())
+
+
+# ------------------------------------------------------------------------------------------------ the volume
+class TsdfVolume:
+    """Dense block table + voxel pool through the library (include/surfel_mesh.h).  `budget_bytes` bounds table + pool."""
+
+    def __init__(self, voxel_size, sdf_trunc, origin, dims, budget_bytes, device):
+        self.lib, self.device = _n.load(), torch.device(device)
+        self.alloc = _n.TorchAllocator(self.device)
+        self.v = _n.TsdfVolume()
+        self.v.origin[:] = [int(x) for x in origin]
+        self.v.dims[:] = [int(x) for x in dims]
+        self.v.voxel_size, self.v.sdf_trunc, self.v.budget_bytes = float(voxel_size), float(sdf_trunc), int(budget_bytes)
+        self._call("surfel_tsdf_init", self.lib.surfel_tsdf_init, C.byref(self.v), self.alloc.cb, None, self._s())
+
+    def _s(self):
+        return _n.current_stream_ptr(self.device)
+
+    def _call(self, what, fn, *args):
+        with torch.cuda.device(self.device):
+            rc = fn(*args)
+        if rc == -4:
+            raise MeshLimitError("%s: %s" % (what, _n.last_error()))
+        return _check(rc, what)
+
+    def mark(self, depth, cam):
+        H, W = depth.shape[-2:]
+        self._call("surfel_tsdf_mark", self.lib.surfel_tsdf_mark, C.byref(self.v), H, W, _n.ptr(depth), _n.ptr(cam), self._s())
+
+    def allocate(self):
+        return self._call("surfel_tsdf_allocate", self.lib.surfel_tsdf_allocate, C.byref(self.v), self.alloc.cb, None, self._s())
+
+    def integrate(self, depth, rgba, cam):
+        H, W = depth.shape[-2:]
+        self._call("surfel_tsdf_integrate", self.lib.surfel_tsdf_integrate, C.byref(self.v), H, W, _n.ptr(depth), _n.ptr(rgba), _n.ptr(cam), self._s())
+
+    def extract(self):
+        self._call("surfel_tsdf_count", self.lib.surfel_tsdf_count, C.byref(self.v), self._s())
+        V, F = int(self.v.nverts), int(self.v.ntris)
+        verts = torch.empty((V, 3), dtype=torch.float32, device=self.device)
+        cols = torch.empty((V, 3), dtype=torch.float32, device=self.device)
+        tris = torch.empty((F, 3), dtype=torch.int32, device=self.device)
+        self._call("surfel_tsdf_extract", self.lib.surfel_tsdf_extract, C.byref(self.v), _n.ptr(verts), _n.ptr(cols), _n.ptr(tris), self._s())
+        return TriangleMesh(verts, tris, cols)
+
+    def _tensor(self, field, dtype, shape):
+        """A view of one of the library's buffers (white-box access for tests and measurement)."""
+        p = getattr(self.v, field)
+        for t in self.alloc.held:
+            if t.data_ptr() == p:
+                return t[:int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(*shape)
+        raise KeyError(field)
+
+    def blocks(self):
+        """(block coordinates [nblocks,3] int64 in slot order = table order, tsdf_rgb [nblocks,4096,4], weight [nblocks,4096])"""
+        nb = int(self.v.nblocks)
+        if nb == 0:
+            return np.zeros((0, 3), np.int64), torch.zeros((0, 4096, 4)), torch.zeros((0, 4096))
+        keys = self._tensor("keys", torch.int32, (nb,)).cpu().numpy().astype(np.int64)
+        nx, ny, _ = self.v.dims
+        bc = np.stack([keys % nx, (keys // nx) % ny, keys // (nx * ny)], 1) + np.array(self.v.origin)
+        return bc, self._tensor("tsdf_rgb", torch.float32, (nb, 4096, 4)), self._tensor("weight", torch.float32, (nb, 4096))
+
+
+def volume_bounds(cams_blocks, depth_trunc, sdf_trunc, voxel_size):
+    """Dense block table from the cameras alone: their centres' AABB grown by depth_trunc * (largest ray stretch) + sdf_trunc, in
+    blocks of 16 voxels.  cams_blocks: [N,16] camera blocks with the image sizes appended ([N,18])."""
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for c in cams_blocks:
+        ext = np.eye(4)
+        ext[:3, :4] = np.asarray(c[:12], np.float64).reshape(3, 4)
+        centre = np.linalg.inv(ext)[:3, 3]
+        fx, fy, cx, cy, W, H = (float(x) for x in c[12:18])
+        stretch = math.sqrt(1.0 + (max(cx, W - 1 - cx) / fx) ** 2 + (max(cy, H - 1 - cy) / fy) ** 2)
+        g = depth_trunc * stretch + sdf_trunc
+        lo, hi = np.minimum(lo, centre - g), np.maximum(hi, centre + g)
+    bs = 16.0 * voxel_size
+    b0 = np.floor(lo / bs).astype(np.int64) - 1
+    b1 = np.floor(hi / bs).astype(np.int64) + 1
+    return b0, b1 - b0 + 1
+
+
+def fuse(depths, rgbas, cams, voxel_size, sdf_trunc, depth_trunc, budget_bytes, device, timings=None, touched=None):
+    """TSDF fusion of prepared views (depth [H,W] with 0 = invalid, rgba [H,W] uint32, camera block [16]) into a TsdfVolume.
+    touched: a list that receives every view's touched-block count (synchronises after each view; measurement only)."""
+    dev = torch.device(device)
+    blocks = [np.concatenate([c.cpu().numpy(), [d.shape[-1], d.shape[-2]]]) for c, d in zip(cams, depths)]
+    origin, dims = volume_bounds(blocks, depth_trunc, sdf_trunc, voxel_size)
+    if np.any(dims > 2 ** 20) or int(np.prod(dims)) * 8 > budget_bytes:
+        raise MeshLimitError("mesh volume: the dense block table (%s blocks) exceeds the byte budget (%d)" % (list(dims), budget_bytes))
+    t = _Timer(timings, dev)
+    vol = TsdfVolume(voxel_size, sdf_trunc, origin, dims, budget_bytes, dev)
+    for d, c in zip(depths, cams):
+        vol.mark(d, c)
+    vol.allocate()
+    t.lap("touch")
+    for d, rgba, c in zip(depths, rgbas, cams):
+        vol.integrate(d, rgba, c)
+        if touched is not None:
+            touched.append(int(vol._tensor("list", torch.int32, (1,))[0]) if vol.v.nblocks else 0)
+    t.lap("integrate")
+    return vol
+
+
+class _Timer:
+    def __init__(self, out, dev):
+        self.out, self.dev = out, dev
+        if out is not None:
+            torch.cuda.synchronize(dev)
+            self.t = time.perf_counter()
+
+    def lap(self, name):
+        if self.out is None:
+            return
+        torch.cuda.synchronize(self.dev)
+        now = time.perf_counter()
+        self.out[name] = self.out.get(name, 0.0) + (now - self.t) * 1e3
+        self.t = now
+
+
+def prepare_view(surf_depth, rgb, mask, depth_trunc):
+    """(depth [H,W] float32, rgba [H,W] int32) of one view (surfel_mesh_prepare_view)."""
+    d = surf_depth.detach().contiguous().float()
+    H, W = d.shape[-2:]
+    rgb = rgb.detach().contiguous().float()
+    m = None if mask is None else mask.detach().contiguous().float().to(d.device)
+    dout = torch.empty((H, W), dtype=torch.float32, device=d.device)
+    rgba = torch.empty((H, W), dtype=torch.int32, device=d.device)
+    with torch.cuda.device(d.device):
+        _check(_n.load().surfel_mesh_prepare_view(H, W, _n.ptr(d), _n.ptr(rgb), _n.ptr(m), float(depth_trunc), _n.ptr(dout), _n.ptr(rgba),
+                                                  _n.current_stream_ptr(d.device)), "surfel_mesh_prepare_view")
+    return dout, rgba
+
+
+# ------------------------------------------------------------------------------------------------ the reference's interface
+DEFAULT_BUDGET = 64 << 30
+
+
+class GaussianExtractor:
+    """utils/mesh_utils.py:72-181, bounded path: render(viewpoint_cam, gaussians, pipe, bg_color) must return the reference's dict."""
+
+    def __init__(self, gaussians, render, pipe, bg_color=None):
+        if bg_color is None:
+            bg_color = [0, 0, 0]
+        dev = gaussians.get_xyz.device if hasattr(gaussians, "get_xyz") else torch.device("cuda")
+        self.gaussians = gaussians
+        self.background = torch.tensor(bg_color, dtype=torch.float32, device=dev)
+        self.render = lambda cam, g: render(cam, g, pipe, self.background)
+        self.budget_bytes = DEFAULT_BUDGET
+        self.timings = None
+        self.clean()
+
+    def clean(self):
+        self.depthmaps, self.rgbmaps, self.viewpoint_stack = [], [], []
+
+    @torch.no_grad()
+    def reconstruction(self, viewpoint_stack):
+        """Renders every view; surf_depth and render stay on the device."""
+        self.clean()
+        self.viewpoint_stack = viewpoint_stack
+        t = _Timer(self.timings, self.background.device)
+        for cam in self.viewpoint_stack:
+            pkg = self.render(cam, self.gaussians)
+            self.rgbmaps.append(pkg["render"].detach())
+            self.depthmaps.append(pkg["surf_depth"].detach())
+        t.lap("render")
+        self.estimate_bounding_sphere()
+
+    def estimate_bounding_sphere(self):
+        c2ws = np.array([np.linalg.inv(np.asarray(cam.world_view_transform.detach().cpu().numpy(), np.float64).T) for cam in self.viewpoint_stack])
+        center, self.radius = bounding_sphere(c2ws)
+        self.center = torch.from_numpy(center).float().to(self.background.device)
+        print("The estimated bounding radius is %.2f" % self.radius)
+        print("Use at least %.2f for depth_trunc" % (2.0 * self.radius))
+
+    @torch.no_grad()
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True):
+        """TSDF fusion of every reconstructed view and marching cubes (MESH.md).  Returns a TriangleMesh on the device."""
+        depths, rgbas, cams = [], [], []
+        for i, cam in enumerate(self.viewpoint_stack):
+            mask = getattr(cam, "gt_alpha_mask", None) if mask_backgrond else None
+            d, rgba = prepare_view(self.depthmaps[i], self.rgbmaps[i], mask, depth_trunc)
+            depths.append(d); rgbas.append(rgba)
+            cams.append(torch.from_numpy(camera_block(cam)).to(d.device))
+        vol = fuse(depths, rgbas, cams, voxel_size, sdf_trunc, depth_trunc, self.budget_bytes, self.background.device, self.timings)
+        t = _Timer(self.timings, self.background.device)
+        mesh = vol.extract()
+        t.lap("extract")
+        self.volume = vol
+        return mesh
+
+
+def cluster_triangles(mesh):
+    """(label [F] = smallest triangle id of the triangle's edge-connected cluster, size [F] = triangles per label id)."""
+    tris = mesh.triangles.contiguous()
+    F, V = int(tris.shape[0]), int(mesh.vertices.shape[0])
+    label = torch.empty(F, dtype=torch.int32, device=tris.device)
+    size = torch.empty(F, dtype=torch.int32, device=tris.device)
+    alloc = _n.TorchAllocator(tris.device)
+    with torch.cuda.device(tris.device):
+        _check(_n.load().surfel_mesh_clusters(alloc.cb, None, V, F, _n.ptr(tris), _n.ptr(label), _n.ptr(size), _n.current_stream_ptr(tris.device)),
+               "surfel_mesh_clusters")
+    return label, size
+
+
+def post_process_mesh(mesh, cluster_to_keep=1000):
+    """utils/mesh_utils.py:22-41: keeps the clusters with at least max(k-th largest cluster size, 50) triangles (50 when there are
+    fewer than k clusters), then drops unreferenced vertices (order kept) and triangles that repeat an index."""
+    print("post processing the mesh to have {} clusterscluster_to_kep".format(cluster_to_keep))
+    dev = mesh.triangles.device
+    F, V = int(mesh.triangles.shape[0]), int(mesh.vertices.shape[0])
+    if F == 0:
+        return TriangleMesh(mesh.vertices[:0], mesh.triangles[:0], mesh.vertex_colors[:0])
+    label, size = cluster_triangles(mesh)
+    counts = size[size > 0].sort().values        # one entry per cluster: a few numbers, selected on the device
+    threshold = int(counts[-cluster_to_keep]) if cluster_to_keep <= counts.numel() else 0
+    threshold = max(threshold, 50)
+    vout = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    cout = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    tout = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    n = (C.c_int64 * 2)()
+    alloc = _n.TorchAllocator(dev)
+    with torch.cuda.device(dev):
+        _check(_n.load().surfel_mesh_filter(alloc.cb, None, V, F, _n.ptr(mesh.vertices.contiguous()), _n.ptr(mesh.vertex_colors.contiguous()),
+                                            _n.ptr(mesh.triangles.contiguous()), _n.ptr(label), _n.ptr(size), threshold, _n.ptr(vout), _n.ptr(cout),
+                                            _n.ptr(tout), n, _n.current_stream_ptr(dev)), "surfel_mesh_filter")
+    print("num vertices raw {}".format(V))
+    print("num vertices post {}".format(int(n[0])))
+    return TriangleMesh(vout[:n[0]], tout[:n[1]], cout[:n[0]])
+
+
+# ------------------------------------------------------------------------------------------------ CLI (render.py:86-106)
+def _latest_iteration(model_dir):
+    its = [int(d.split("_")[-1]) for d in os.listdir(os.path.join(model_dir, "point_cloud")) if d.startswith("iteration_")]
+    if not its:
+        raise FileNotFoundError("no point_cloud/iteration_* under %s" % model_dir)
+    return max(its)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Bounded TSDF mesh of a trained model (render.py's mesh step). Unlike the reference, which "
+                                             "fuses only the training split, every camera in cameras.json is fused.")
+    ap.add_argument("-m", "--model_path", required=True)
+    ap.add_argument("--iteration", default=-1, type=int)
+    ap.add_argument("--voxel_size", default=-1.0, type=float, help="Mesh: voxel size for TSDF (default depth_trunc / mesh_res)")
+    ap.add_argument("--depth_trunc", default=-1.0, type=float, help="Mesh: max depth range for TSDF (default 2 x bounding radius)")
+    ap.add_argument("--sdf_trunc", default=-1.0, type=float, help="Mesh: truncation value for TSDF (default 5 x voxel_size)")
+    ap.add_argument("--num_cluster", default=50, type=int, help="Mesh: number of connected clusters to export")
+    ap.add_argument("--mesh_res", default=1024, type=int, help="Mesh: resolution for unbounded mesh extraction")
+    ap.add_argument("--depth_ratio", default=0.0, type=float)
+    ap.add_argument("--white_background", action="store_true")
+    ap.add_argument("--budget_gb", default=DEFAULT_BUDGET / 2 ** 30, type=float, help="byte budget of the TSDF volume (GiB)")
+    args = ap.parse_args(argv)
+    import surfel_io
+    import surfel_model
+    from surfel_render import render
+    dev = torch.device("cuda")
+    it = _latest_iteration(args.model_path) if args.iteration < 0 else args.iteration
+    gaussians = surfel_model.GaussianModel(3, device=dev)
+    gaussians.load_ply(os.path.join(args.model_path, "point_cloud", "iteration_%d" % it, "point_cloud.ply"))
+    cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=dev)
+    pipe = argparse.Namespace(depth_ratio=args.depth_ratio, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
+    ext = GaussianExtractor(gaussians, render, pipe, bg_color=[1, 1, 1] if args.white_background else [0, 0, 0])
+    ext.budget_bytes = int(args.budget_gb * 2 ** 30)
+    out = os.path.join(args.model_path, "train", "ours_%d" % it)
+    os.makedirs(out, exist_ok=True)
+    gaussians.active_sh_degree = 0      # render.py:91: diffuse colour only
+    ext.reconstruction(cams)
+    depth_trunc = ext.radius * 2.0 if args.depth_trunc < 0 else args.depth_trunc
+    voxel_size = depth_trunc / args.mesh_res if args.voxel_size < 0 else args.voxel_size
+    sdf_trunc = 5.0 * voxel_size if args.sdf_trunc < 0 else args.sdf_trunc
+    mesh = ext.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc)
+    surfel_io.write_triangle_mesh(os.path.join(out, "fuse.ply"), mesh)
+    print("mesh saved at {}".format(os.path.join(out, "fuse.ply")))
+    post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
+    surfel_io.write_triangle_mesh(os.path.join(out, "fuse_post.ply"), post)
+    print("mesh post processed saved at {}".format(os.path.join(out, "fuse_post.ply")))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -24,6 +24,9 @@ EXPORTS = ["surfel_abi_version", "surfel_last_error", "surfel_rasterize_forward"
            # include/surfel_train.h
            "surfel_l1_ssim_forward", "surfel_l1_ssim_backward", "surfel_l1_ssim_forward_w", "surfel_l1_ssim_backward_w", "surfel_render_post_forward", "surfel_render_post_backward", "surfel_train_loss_forward", "surfel_train_loss_backward",
            "surfel_reduce_partials", "surfel_loss_finalize", "surfel_activate", "surfel_adam_step", "surfel_train_update", "surfel_sh_grad_gather", "surfel_densify_stats"]
+# include/surfel_mesh.h
+MESH_EXPORTS = ["surfel_tsdf_table_bytes", "surfel_tsdf_block_bytes", "surfel_mesh_prepare_view", "surfel_tsdf_init", "surfel_tsdf_mark", "surfel_tsdf_allocate",
+                "surfel_tsdf_integrate", "surfel_tsdf_count", "surfel_tsdf_extract", "surfel_mesh_clusters", "surfel_mesh_filter"]
 
 # per-call option overrides carried in the upper bits of the `debug` argument (include/surfel_hip.h)
 OPT_NO_CULL = 1 << 8
@@ -49,6 +52,14 @@ def opt_tile_order(mode):
 
 def opt_tile_sort(mode):
     return ((mode + 1) & 3) << 9
+
+
+class TsdfVolume(C.Structure):
+    """surfel_tsdf_volume of include/surfel_mesh.h"""
+    _fields_ = [("origin", C.c_int * 3), ("dims", C.c_int * 3), ("voxel_size", C.c_float), ("sdf_trunc", C.c_float), ("budget_bytes", C.c_int64),
+                ("table", C.c_void_p), ("scratch", C.c_void_p), ("nblocks", C.c_int64), ("keys", C.c_void_p), ("stamp", C.c_void_p),
+                ("list", C.c_void_p), ("tsdf_rgb", C.c_void_p), ("weight", C.c_void_p), ("info", C.c_void_p), ("vbase", C.c_void_p),
+                ("tbase", C.c_void_p), ("pool_scratch", C.c_void_p), ("views", C.c_int64), ("nverts", C.c_int64), ("ntris", C.c_int64)]
 
 
 _lib = None
@@ -121,6 +132,21 @@ def load():
                            ("surfel_densify_stats", [i, vp, vp, vp, vp, vp, vp])):
             fn = getattr(lib, name)
             fn.restype = i
+            fn.argtypes = args
+        # ---- include/surfel_mesh.h
+        vol = C.POINTER(TsdfVolume)
+        for name, res, args in (("surfel_tsdf_table_bytes", i64, [vol]), ("surfel_tsdf_block_bytes", i64, []),
+                                ("surfel_mesh_prepare_view", i, [i, i, vp, vp, vp, f, vp, vp, vp]),
+                                ("surfel_tsdf_init", i, [vol, ALLOC_FN, vp, vp]),
+                                ("surfel_tsdf_mark", i, [vol, i, i, vp, vp, vp]),
+                                ("surfel_tsdf_allocate", i64, [vol, ALLOC_FN, vp, vp]),
+                                ("surfel_tsdf_integrate", i, [vol, i, i, vp, vp, vp, vp]),
+                                ("surfel_tsdf_count", i, [vol, vp]),
+                                ("surfel_tsdf_extract", i, [vol, vp, vp, vp, vp]),
+                                ("surfel_mesh_clusters", i, [ALLOC_FN, vp, i64, i64, vp, vp, vp, vp]),
+                                ("surfel_mesh_filter", i, [ALLOC_FN, vp, i64, i64, vp, vp, vp, vp, vp, i, vp, vp, vp, C.POINTER(C.c_int64), vp])):
+            fn = getattr(lib, name)
+            fn.restype = res
             fn.argtypes = args
         if lib.surfel_abi_version() != 1:
             raise ImportError("libsurfel_hip.so ABI version mismatch")
