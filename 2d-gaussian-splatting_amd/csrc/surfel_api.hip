@@ -1,7 +1,6 @@
 // surfel_api.hip — C ABI (include/surfel_hip.h) of libsurfel_hip.so: stage orchestration, scratch
 // carving.  Host code only; kernels live in surfel_forward.hip,
 // surfel_backward.hip and knn.hip.
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -18,45 +17,48 @@ using namespace surfel;
 
 namespace {
 
-thread_local std::string g_err;
-int g_opt_cull = 1;        // surfel_set_option("cull", .)
-int g_opt_tile_sort = 1;   // surfel_set_option("tile_depth_sort", .): 0 never, 1 auto (by last frame's R / tiles), 2 always
-int g_opt_bwd_variant = 2; // surfel_set_option("bwd_variant", .): 0 per-row walk, 1 per-quad walk (0 / 1 bit-identical), 2 auto = rows or scan by the device rule, 3 scan walk
-surfel_hook_fn g_colour_hook = nullptr;   // surfel_set_backward_hook
-void* g_colour_hook_user = nullptr;
-int g_opt_stream = 1;      // surfel_set_option("tile_stream", .): blend_fwd leaves the tile stream for blend_bwd (surfel_common.h); 0: blend_bwd gathers
-unsigned long long* g_blend_stats = nullptr;   // surfel_debug_set_blend_stats
-thread_local int64_t g_last_R = -1; thread_local int g_last_W = 0, g_last_H = 0;   // auto heuristic (speed only; results identical; a stale
-                                                                                    // value from another device / stream only costs one slower frame)
+const char* kStageNames[] = {"preprocess_fwd", "depth_sort_scan", "emit_instances", "tile_sort", "tile_ranges", "blend_fwd",
+                             "zero_grec", "blend_bwd", "preprocess_bwd", "knn", "tile_depth_sort"};
+enum Stage { ST_PRE = 0, ST_SCAN, ST_EMIT, ST_SORT, ST_RANGES, ST_BLEND, ST_ZERO, ST_BBWD, ST_PBWD, ST_KNN, ST_TSORT, ST_COUNT };
+static_assert(sizeof(kStageNames) / sizeof(kStageNames[0]) == ST_COUNT, "one name per stage");
+
 // capacity binning: the largest instance count recent frames of a size produced (per host thread; speed only)
 // (16 entries: a COLMAP capture mixes a handful of resolutions; an evicted size falls back to the exact path + a host wait for one
 // frame — counted, surfel_debug_capacity_evictions.  boost: head room doubles (1/8 -> 1/4 -> 1/2) while frames of the size keep
 // overflowing — views of one capture differ 2-3x in instance count — and decays after 256 frames without an overflow.)
-struct CapEntry { int W = 0, H = 0; int64_t maxR = -1; unsigned frames = 0; int uniform_streak = 0; int boost = 0; unsigned last_overflow = 0; };
+struct CapEntry {
+    int W = 0, H = 0; int64_t maxR = -1; unsigned frames = 0; int uniform_streak = 0; int boost = 0; unsigned last_overflow = 0;
+    int slot() const; void begin_frame(); int64_t capacity(int end_bit) const; void record_count(int64_t R, bool overflowed);
+};
 constexpr int kCapEntries = 16;
-thread_local CapEntry g_caps[kCapEntries];
-thread_local unsigned g_cap_next = 0;
-thread_local int g_cap_evictions = 0;
+
+// One event + one pinned read-back buffer per (host thread, device): a thread that rasterizes on a second GPU gets its own pair
+// instead of recording an event created on another device.
+constexpr int kMaxDevices = 32;
+constexpr int kPinnedTotal = R_SLOTS + kCapEntries;      // word of the pinned buffer that receives a capacity-path frame's instance total
+struct PerDevice { hipEvent_t ev = nullptr; uint32_t* pinned = nullptr; };
+
+// ---- Per host thread (g_lazy, the lazily counted frame, is too: it sits with lazy_finish, in the extern "C" block) ----
+thread_local std::string g_err;
+struct ThreadState {
+    int64_t last_R = -1; int last_W = 0, last_H = 0;   // auto heuristic (speed only; a stale value from another device / stream costs one slower frame)
+    CapEntry caps[kCapEntries]; unsigned cap_next = 0; int cap_evictions = 0;
+    int last_binning = 0;      // 0 exact-size path, 1 capacity path, 2 capacity path overflowed and redone, 4 lazily counted (surfel_debug_last_binning)
+    float stage_ms[16] = {}; int stage_id[16] = {}; int stage_n = 0;
+    PerDevice dev[kMaxDevices];
+};
+thread_local ThreadState g_th;
+
+// ---- Process-wide: the options, the hooks, the stream registry and the pending stage timers below ----
+int g_opt_cull = 1;        // surfel_set_option("cull", .)
+int g_opt_tile_sort = 1;   // surfel_set_option("tile_depth_sort", .): 0 never, 1 auto (by last frame's R / tiles), 2 always
+int g_opt_bwd_variant = 2; // surfel_set_option("bwd_variant", .): 0 per-row walk, 1 per-quad walk (0 / 1 bit-identical), 2 auto = rows or scan by the device rule, 3 scan walk
+int g_opt_stream = 1;      // surfel_set_option("tile_stream", .): blend_fwd leaves the tile stream for blend_bwd (surfel_common.h); 0: blend_bwd gathers
 int g_opt_capacity = 1;    // surfel_set_option("capacity_binning", .)
 int g_opt_tile_order = 0;  // surfel_set_option("tile_order", .): 0 decided per frame on the device, 1 XCD-contiguous runs, 2 longest lists first
-thread_local int g_last_binning = 0;      // 0 exact-size path, 1 capacity path, 2 capacity path overflowed and the frame was redone (surfel_debug_last_binning)
-CapEntry* cap_entry(int W, int H, bool create) {
-    for (auto& c : g_caps) if (c.W == W && c.H == H) return &c;
-    if (!create) return nullptr;
-    CapEntry* c = &g_caps[g_cap_next++ % kCapEntries];
-    if (c->W != 0) g_cap_evictions++;
-    *c = CapEntry{};
-    c->W = W; c->H = H;
-    c->frames = ~0u;      // (marks "just created": the caller clears the slot's pinned tile-order verdict, run_tile_order)
-    return c;
-}
-thread_local float g_stage_ms[16];
-thread_local int g_stage_n = 0;
-thread_local int g_stage_id[16];
-
-const char* kStageNames[] = {"preprocess_fwd", "depth_sort_scan", "emit_instances", "tile_sort", "tile_ranges", "blend_fwd",
-                             "zero_grec", "blend_bwd", "preprocess_bwd", "knn", "tile_depth_sort"};
-enum Stage { ST_PRE = 0, ST_SCAN, ST_EMIT, ST_SORT, ST_RANGES, ST_BLEND, ST_ZERO, ST_BBWD, ST_PBWD, ST_KNN, ST_TSORT };
+surfel_hook_fn g_colour_hook = nullptr;   // surfel_set_backward_hook
+void* g_colour_hook_user = nullptr;
+unsigned long long* g_blend_stats = nullptr;   // surfel_debug_set_blend_stats
 
 int fail(int code, const char* what, hipError_t e = hipSuccess) {
     g_err = what;
@@ -91,7 +93,7 @@ struct GeomState {   // per-surfel state ("geomBuffer")
     uint32_t* offsets;                            // inclusive scan of tiles_touched in depth order
     uint32_t* rects;                              // packed tile rect of every surfel (copy of record word 19: emission reads 4 B instead of a record line)
     float* shjac;                                 // [9][P]: d(SH colour) / d(view direction) planes for preprocess_bwd (written unless SURFEL_OPT_NO_STREAM)
-    char* temp; size_t temp_bytes;                // scratch of the P-sized sort, then of the scan
+    char* temp;                                   // scratch of the P-sized sort, then of the scan
     static GeomState carve(void* base, int P, size_t temp_bytes, size_t* total) {
         Carver c(base); GeomState g;
         g.rec = c.take<float>((size_t)P * REC_F);
@@ -104,14 +106,13 @@ struct GeomState {   // per-surfel state ("geomBuffer")
         g.rects = c.take<uint32_t>(P);
         g.shjac = c.take<float>((size_t)9 * P);
         g.temp = c.take<char>(temp_bytes);
-        g.temp_bytes = temp_bytes;
         if (total) *total = c.size();
         return g;
     }
 };
 
 struct BinState {    // per-instance state ("binningBuffer"); point_list is always at a fixed offset
-    uint32_t* point_list; uint32_t* vals_alt; uint32_t* keys_a; uint32_t* keys_b; char* sort_temp; size_t sort_temp_bytes;
+    uint32_t* point_list; uint32_t* vals_alt; uint32_t* keys_a; uint32_t* keys_b; char* sort_temp;
     float4* strm_rec = nullptr; uint32_t* strm_mask = nullptr;      // the tile stream (surfel_common.h), or NULL
     static bool wants_stream(size_t R) { return g_opt_stream != 0 && R > 0 && (long long)R <= STRM_MAX_R; }
     // stream: the forward's decision (wants_stream of ITS capacity); the backward never carves it — it is called with the exact count
@@ -127,7 +128,6 @@ struct BinState {    // per-instance state ("binningBuffer"); point_list is alwa
             b.strm_mask = c.take<uint32_t>(R);
         }
         b.sort_temp = c.take<char>(sort_bytes);
-        b.sort_temp_bytes = sort_bytes;
         if (total) *total = c.size();
         return b;
     }
@@ -219,7 +219,7 @@ struct StageTimer {
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
         float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
-        if (g_stage_n < 16) { g_stage_ms[g_stage_n] = ms; g_stage_id[g_stage_n] = stage; g_stage_n++; }
+        if (g_th.stage_n < 16) { g_th.stage_ms[g_th.stage_n] = ms; g_th.stage_id[g_th.stage_n] = stage; g_th.stage_n++; }
         return 0;
     }
 };
@@ -229,17 +229,11 @@ struct StageTimer {
         if (_e) return fail(SURFEL_E_HIP, kStageNames[st], (hipError_t)_e);                \
     } while (0)
 
-// One event + one pinned read-back buffer per (host thread, device): a thread that rasterizes on a second GPU gets its own pair
-// instead of recording an event created on another device.
-constexpr int kMaxDevices = 32;
-constexpr int kPinnedTotal = R_SLOTS + kCapEntries;      // word of the pinned buffer that receives a capacity-path frame's instance total
-struct PerDevice { hipEvent_t ev = nullptr; uint32_t* pinned = nullptr; };
 PerDevice* per_device(int dev = -1) {      // dev < 0: the calling thread's current device
-    thread_local PerDevice tab[kMaxDevices];
     int d = dev;
     if (d < 0 && hipGetDevice(&d) != hipSuccess) return nullptr;
     if (d < 0 || d >= kMaxDevices) return nullptr;
-    return &tab[d];
+    return &g_th.dev[d];
 }
 
 hipEvent_t r_event() {
@@ -261,6 +255,45 @@ uint32_t* pinned_u32() {
     return pd->pinned;
 }
 
+// a frame's instance count in the pinned buffer: stored by bin_emit_kernel (capacity path), or the R_SLOTS partial totals copied there
+int64_t pinned_total(const uint32_t* hR, bool host_total) {
+    if (host_total) return (int64_t)hR[kPinnedTotal];
+    int64_t R = 0;
+    for (int k = 0; k < R_SLOTS; k++) R += (int64_t)hR[k];
+    return R;
+}
+
+CapEntry* cap_entry(int W, int H) {
+    for (auto& c : g_th.caps) if (c.W == W && c.H == H) return &c;
+    CapEntry* c = &g_th.caps[g_th.cap_next++ % kCapEntries];
+    if (c->W != 0) g_th.cap_evictions++;
+    *c = CapEntry{};
+    c->W = W; c->H = H;
+    c->frames = ~0u;      // (marks "just created": begin_frame clears the slot's pinned tile-order verdict)
+    return c;
+}
+
+int CapEntry::slot() const { return (int)(this - g_th.caps); }      // (word R_SLOTS + slot of the pinned buffer: the tile-order verdict)
+void CapEntry::begin_frame() {
+    if (frames == ~0u) {      // a (re-)used slot must not inherit the previous size's tile-order verdict
+        frames = 0;
+        if (uint32_t* hv = pinned_u32()) hv[R_SLOTS + slot()] = 0u;
+    }
+    frames++;
+    if (boost > 0 && frames - last_overflow > 256u) { boost--; last_overflow = frames; }
+}
+int64_t CapEntry::capacity(int end_bit) const {      // of this frame's binning buffers; 0: none (the exact path)
+    if (maxR < 0) return 0;
+    int64_t cap = maxR + (maxR >> (3 - boost)) + 4096;
+    cap = (cap + 16383) / 16384 * 16384;      // stable sizes for the caller's caching allocator
+    return (cap > ((int64_t)1 << 20) || !capacity_binning_ok((size_t)cap, end_bit)) ? 0 : cap;
+}
+void CapEntry::record_count(int64_t R, bool overflowed) {      // a frame's exact count; it is also the "last frame" of the per-tile rule
+    g_th.last_R = R; g_th.last_W = W; g_th.last_H = H;
+    if (overflowed) { if (boost < 2) boost++; last_overflow = frames; }
+    maxR = R > maxR - maxR / 64 ? R : maxR - maxR / 64;      // the largest recent count, slowly forgotten
+}
+
 // tile_order_kernel costs ~8 us even when it only finds the frame uniform (one workgroup, a global round trip, the launch itself) —
 // 1.3 % of a C2 step.  Frames of a size that keeps coming out uniform therefore run it only every 8th frame (the blend kernels use
 // the XCD-contiguous order when no map was written); frames with uneven lists, where the map pays, run it always.  The verdicts
@@ -268,14 +301,13 @@ uint32_t* pinned_u32() {
 void run_tile_order(CapEntry* ce, const uint2* ranges, int gx, int gy, int* map, uint32_t* map_flag, int opt, hipStream_t s) {
     if (opt == 1) return;                  // XCD-contiguous order: the flag word is zero
     uint32_t* hv = pinned_u32();
-    const int slot = ce ? (int)(ce - g_caps) : 0;
     uint32_t* verdict = nullptr;
     if (hv && opt == 0) {
-        const uint32_t v = hv[R_SLOTS + slot];
+        const uint32_t v = hv[R_SLOTS + ce->slot()];
         if (v == 1u) ce->uniform_streak = ce->uniform_streak < 1000 ? ce->uniform_streak + 1 : 1000;
         else if (v == 2u) ce->uniform_streak = 0;
         void* dv = nullptr;
-        if (hipHostGetDevicePointer(&dv, hv + R_SLOTS + slot, 0) == hipSuccess) verdict = static_cast<uint32_t*>(dv);
+        if (hipHostGetDevicePointer(&dv, hv + R_SLOTS + ce->slot(), 0) == hipSuccess) verdict = static_cast<uint32_t*>(dv);
         if (verdict && ce->uniform_streak >= 4 && (ce->frames & 7u) != 0u) return;
     }
     launch_tile_order(ranges, gx, gy, map, map_flag, opt, verdict, s);
@@ -285,6 +317,109 @@ int higher_msb(uint32_t n) {   // number of bits needed to represent values < n
     int b = 0;
     while ((1ull << b) < (unsigned long long)n) b++;
     return b < 1 ? 1 : b;
+}
+
+// per-tile depth sort (1) or depth-presorted emission (0) for R instances: bitonic work grows as n log^2 n — at ~1100 instances per
+// tile it costs 0.25 ms vs 0.15 ms for the P-sized radix sort (C4)
+int per_tile_pays(int64_t R, int gx, int gy) { return R <= (int64_t)640 * gx * gy ? 1 : 0; }
+
+int alloc_bin(size_t n, size_t sort_bytes, bool stream, surfel_alloc_fn binning_alloc, void* binning_user, BinState* bin) {
+    const bool strm = stream && BinState::wants_stream(n);
+    size_t bytes = 0;
+    BinState::carve(nullptr, n, sort_bytes, &bytes, strm);
+    void* base = binning_alloc(binning_user, bytes > 0 ? bytes : 256);
+    if (!base) return fail(SURFEL_E_ALLOC, "binning buffer allocation failed");
+    *bin = BinState::carve(base, n, sort_bytes, nullptr, strm);
+    return 0;
+}
+
+// Capacity path: emission into buffers of `cap` instances, then the tile sort and the ranges over the count bin_emit_kernel leaves on
+// the device, then the per-tile depth sort (maxR: its size hint) — nothing waits for the frame's count.
+int bin_capacity(const PreprocessArgs& pa, int end_bit, int64_t cap, int64_t maxR, const GeomState& geom, const BinState& bin,
+                 const ImgState& img, uint32_t* hR, hipEvent_t evR, StageTimer& tm, hipStream_t s) {
+    uint32_t* n_dev = img.total + 2 * R_SLOTS;      // written by bin_emit_kernel
+    const bool odd = radix_sort_result_buffer((size_t)cap, 0, end_bit) == 1;
+    uint32_t* va = odd ? bin.vals_alt : bin.point_list;
+    uint32_t* vb = odd ? bin.point_list : bin.vals_alt;
+    tm.begin();
+    launch_bin_emit(pa.P, geom.tiles_touched, geom.rects, geom.offsets, geom.rec, bin.keys_a, va, pa.gx, (size_t)cap, bin.sort_temp, end_bit,
+                    n_dev, hR + kPinnedTotal, s);
+    HIP_TRY(hipEventRecord(evR, s));
+    STAGE_END(tm, ST_EMIT);
+    tm.begin();
+    // the tile ranges come out of the sort's last pass (its scatter knows every key boundary); frames of one tile have no pass
+    const bool fused_ranges = end_bit > 0;
+    const int wk = radix_sort_pairs_u32_devn(bin.keys_a, va, bin.keys_b, vb, (size_t)cap, end_bit, n_dev, bin.sort_temp, fused_ranges ? img.ranges : nullptr, s);
+    STAGE_END(tm, ST_SORT);
+    if (!fused_ranges) { tm.begin(); launch_tile_ranges_devn((size_t)cap, n_dev, wk ? bin.keys_b : bin.keys_a, img.ranges, s); STAGE_END(tm, ST_RANGES); }
+    tm.begin(); launch_tile_depth_sort(pa.gx * pa.gy, maxR, img.ranges, bin.point_list, geom.dkey_a, bin.vals_alt, bin.keys_a, bin.keys_b, fused_ranges, s);
+    STAGE_END(tm, ST_TSORT);
+    return 0;
+}
+
+// Exact path, sized by the frame's count: the host waits for it behind the depth sort + scan unless it is known (R >= 0: an overflowed
+// capacity frame, per-tile order).  per_tile < 0: the first frame of its size, decided once R has arrived.  Returns R or an error code.
+int64_t bin_exact(const PreprocessArgs& pa, int end_bit, int per_tile, int64_t R, const GeomState& geom, BinState* bin,
+                  const ImgState& img, const uint32_t* hR, hipEvent_t evR, bool stream, surfel_alloc_fn binning_alloc, void* binning_user,
+                  StageTimer& tm, hipStream_t s) {
+    if (per_tile < 0 && R < 0) {         // first frame of this size: wait for R now (loses the host/device overlap once)
+        HIP_TRY(hipEventSynchronize(evR));
+        per_tile = per_tile_pays(pinned_total(hR, false), pa.gx, pa.gy);
+    }
+    tm.begin();
+    const uint32_t* order = geom.ord_a;      // identity (written by preprocess)
+    if (!per_tile) {
+        // (1) surfel order by view depth (stable; culled surfels carry key 0xffffffff and sort last)
+        const int which = radix_sort_pairs_u32(geom.dkey_a, geom.ord_a, geom.dkey_b, geom.ord_b, (size_t)pa.P, 0, 32, geom.temp, s, true);
+        if (which < 0) return fail(SURFEL_E_LIMIT, "too many surfels for the depth sort");
+        order = which ? geom.ord_b : geom.ord_a;
+    }
+    // (2) instance offsets in emission order: inclusive scan of tiles_touched[order[k]] (pa.zero_b: the scan state preprocess cleared)
+    launch_scan_gather(geom.tiles_touched, order, pa.pack_tiles, geom.offsets, (size_t)pa.P, pa.zero_b, s);
+    STAGE_END(tm, ST_SCAN);
+    if (R < 0) {
+        HIP_TRY(hipEventSynchronize(evR));
+        R = pinned_total(hR, false);
+    }
+    if (int e = alloc_bin((size_t)R, radix_sort_scratch_bytes((size_t)R), stream, binning_alloc, binning_user, bin)) return e;
+    if (R == 0) return 0;
+    // (3) stable sort on the tile-id bits only: depth order inside every tile is preserved.  The value buffers
+    // are assigned so that the ping-pong ends in bin->point_list.
+    const bool odd = radix_sort_result_buffer((size_t)R, 0, end_bit) == 1;      // result lands in the b buffers
+    uint32_t* va = odd ? bin->vals_alt : bin->point_list;
+    uint32_t* vb = odd ? bin->point_list : bin->vals_alt;
+    tm.begin();
+    launch_emit_instances(pa.P, geom.rec, geom.rects, order, pa.pack_tiles ? ((1u << PACK_ID_BITS) - 1u) : 0xffffffffu, geom.offsets, bin->keys_a, va, pa.gx,
+                          reinterpret_cast<uint32_t*>(bin->sort_temp), (uint32_t)radix_sort_head_words((size_t)R), s);
+    STAGE_END(tm, ST_EMIT);
+    tm.begin();
+    const int wk = radix_sort_pairs_u32(bin->keys_a, va, bin->keys_b, vb, (size_t)R, 0, end_bit, bin->sort_temp, s, true);
+    if (wk < 0) return fail(SURFEL_E_LIMIT, "too many tile instances for the tile sort");
+    STAGE_END(tm, ST_SORT);
+    tm.begin(); launch_tile_ranges(R, wk ? bin->keys_b : bin->keys_a, img.ranges, s); STAGE_END(tm, ST_RANGES);
+    if (per_tile) {
+        // (4) every tile orders its run by (depth bits, surfel index); the ping-pong buffers of the tile sort are free now
+        tm.begin(); launch_tile_depth_sort(pa.gx * pa.gy, R, img.ranges, bin->point_list, geom.dkey_a, bin->vals_alt, bin->keys_a, bin->keys_b, false, s);
+        STAGE_END(tm, ST_TSORT);
+    }
+    return R;
+}
+
+// avg_list (0 where the host does not know the count) picks the blend kernel, and with it whether the tile stream is written
+int blend(CapEntry* ce, int W, int H, int gx, int gy, const ImgState& img, const void* img_base, const BinState& bin, const float* rec,
+          const float* background, float* out_color, float* out_others, int avg_list, bool jac, int tile_order, StageTimer& tm, hipStream_t s) {
+    run_tile_order(ce, img.ranges, gx, gy, img.tile_map, img.total + 2 * R_SLOTS + 1, tile_order, s);
+    BlendFwdArgs ba{};
+    ba.W = W; ba.H = H; ba.gx = gx; ba.gy = gy;
+    ba.ranges = img.ranges; ba.point_list = bin.point_list; ba.rec = rec; ba.bg = background;
+    ba.out_color = out_color; ba.out_others = out_others; ba.final_T = img.final_T; ba.n_contrib = img.n_contrib;
+    ba.tile_map = img.tile_map; ba.map_flag = img.total + 2 * R_SLOTS + 1; ba.map_len = tile_map_len(gx, gy);
+    ba.stats = g_blend_stats;
+    ba.avg_list = avg_list;
+    ba.strm_rec = bin.strm_rec; ba.strm_mask = bin.strm_mask; ba.totals = img.total; ba.walk_word = img.total + 2 * R_SLOTS + 2;
+    stream_register(bin.point_list, img_base, launch_blend_fwd_writes_stream(ba) ? bin.strm_rec : nullptr, bin.strm_mask, jac);
+    tm.begin(); launch_blend_fwd(ba, s); STAGE_END(tm, ST_BLEND);
+    return 0;
 }
 
 }  // namespace
@@ -297,15 +432,15 @@ extern "C" {
 
 int surfel_abi_version(void) { return SURFEL_ABI_VERSION; }
 const char* surfel_last_error(void) { return g_err.c_str(); }
-const char* surfel_stage_name(int stage) { return (stage >= 0 && stage < 11) ? kStageNames[stage] : "?"; }
+const char* surfel_stage_name(int stage) { return (stage >= 0 && stage < ST_COUNT) ? kStageNames[stage] : "?"; }
 int surfel_last_stage_ms(float* ms, int cap) {
-    int n = g_stage_n < cap ? g_stage_n : cap;
-    for (int i = 0; i < n; i++) ms[i] = g_stage_ms[i];
+    int n = g_th.stage_n < cap ? g_th.stage_n : cap;
+    for (int i = 0; i < n; i++) ms[i] = g_th.stage_ms[i];
     return n;
 }
 int surfel_last_stage_ids(int* ids, int cap) {
-    int n = g_stage_n < cap ? g_stage_n : cap;
-    for (int i = 0; i < n; i++) ids[i] = g_stage_id[i];
+    int n = g_th.stage_n < cap ? g_th.stage_n : cap;
+    for (int i = 0; i < n; i++) ids[i] = g_th.stage_id[i];
     return n;
 }
 
@@ -348,8 +483,8 @@ int surfel_set_backward_hook(surfel_hook_fn colour_ready, void* user) {
     return 0;
 }
 
-int surfel_debug_last_binning(void) { return g_last_binning; }
-int surfel_debug_capacity_evictions(void) { return g_cap_evictions; }
+int surfel_debug_last_binning(void) { return g_th.last_binning; }
+int surfel_debug_capacity_evictions(void) { return g_th.cap_evictions; }
 
 int surfel_debug_image_layout(int width, int height, int64_t* out) {      // host arithmetic only: no device is touched
     if (width <= 0 || height <= 0 || !out) return fail(SURFEL_E_INVALID, "bad arguments");
@@ -376,13 +511,13 @@ int surfel_collect_stage_ms(float* sum_ms, int* count, int cap) {
         (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1);
     }
     g_pending.clear();
-    return 11;
+    return ST_COUNT;
 }
 
 // Lazily counted frames (SURFEL_OPT_LAZY_COUNT): a capacity-path forward that did not wait for its instance count.  The count is
 // collected by surfel_forward_count() — or by the next forward of this thread, which refuses to go on if that frame had overflowed
 // its capacity without anybody looking (its images were built from truncated lists).
-struct LazyPending { bool pending = false; int W = 0, H = 0, dev = -1; int64_t cap = 0; bool overflowed = false, host_total = false; int64_t R = 0; };
+struct LazyPending { bool pending = false; int W = 0, H = 0, dev = -1; int64_t cap = 0; bool overflowed = false; int64_t R = 0; };
 thread_local LazyPending g_lazy;
 
 // waits for the pending count; returns the exact instance count (>= 0) and updates the per-size history, or a negative code
@@ -394,17 +529,13 @@ int64_t lazy_finish() {
     hipEvent_t evR = pd ? pd->ev : nullptr;
     if (!hR || !evR) return fail(SURFEL_E_HIP, "pinned buffer / event of the lazily counted frame's device not found");
     HIP_TRY(hipEventSynchronize(evR));
-    int64_t R = 0;
-    if (g_lazy.host_total) R = (int64_t)hR[kPinnedTotal];
-    else for (int k = 0; k < R_SLOTS; k++) R += (int64_t)hR[k];
+    const int64_t R = pinned_total(hR, true);      // (a lazily counted frame took the capacity path)
     g_lazy.pending = false;
     g_lazy.R = R;
     g_lazy.overflowed = R > g_lazy.cap;
-    g_last_R = R; g_last_W = g_lazy.W; g_last_H = g_lazy.H;
-    CapEntry* ce = cap_entry(g_lazy.W, g_lazy.H, true);
+    CapEntry* ce = cap_entry(g_lazy.W, g_lazy.H);
     if (ce->frames == ~0u) ce->frames = 0;
-    if (g_lazy.overflowed) { if (ce->boost < 2) ce->boost++; ce->last_overflow = ce->frames; }
-    ce->maxR = R > ce->maxR - ce->maxR / 64 ? R : ce->maxR - ce->maxR / 64;
+    ce->record_count(R, g_lazy.overflowed);
     return R;
 }
 
@@ -426,7 +557,7 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
                                  const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                                  float* out_others, int* radii, int debug, void* stream) {
     (void)tan_fovx; (void)tan_fovy; (void)prefiltered;
-    g_stage_n = 0;
+    g_th.stage_n = 0;
     if (g_lazy.pending) { const int64_t r = lazy_finish(); if (r < 0) return r; }
     if (g_lazy.overflowed) {
         g_lazy.overflowed = false;
@@ -439,9 +570,8 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
     const int opt_capacity = (debug & SURFEL_OPT_EXACT_BINNING) ? 0 : g_opt_capacity;
     const int opt_tile_order = ((debug >> 19) & 3) ? ((debug >> 19) & 3) - 1 : g_opt_tile_order;
     const bool opt_stream = !(debug & SURFEL_OPT_NO_STREAM);      // (the caller knows no backward follows: render.py-style inference, no_grad re-renders)
-    const int map_len = tile_map_len((width + TILE - 1) / TILE, (height + TILE - 1) / TILE);
     debug &= 0xff;
-    g_last_binning = 0;
+    g_th.last_binning = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!geom_alloc || !binning_alloc || !image_alloc) return fail(SURFEL_E_INVALID, "allocator callback is NULL");
     if (P < 0 || width <= 0 || height <= 0) return fail(SURFEL_E_INVALID, "bad sizes");
@@ -456,7 +586,6 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
     if (!background || !out_color || !out_others) return fail(SURFEL_E_INVALID, "required pointer is NULL");
     const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
     if (gx > 1023 || gy > 1023) return fail(SURFEL_E_LIMIT, "image larger than 16368 px per side");
-    const size_t HW = (size_t)width * height;
 
     size_t img_bytes = 0;
     ImgState::carve(nullptr, width, height, &img_bytes);
@@ -467,17 +596,17 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
     HIP_TRY(hipMemsetAsync(img.ranges, 0, (size_t)(reinterpret_cast<char*>(img.final_T) - reinterpret_cast<char*>(img.ranges)), s));
 
     StageTimer tm(debug, s);
+    const bool jac = P > 0 && opt_stream && shs != nullptr && M == 16;      // preprocess leaves the d(SH colour) / d(direction) rows
+    CapEntry* ce = cap_entry(width, height);      // per-size history (capacity, tile-order verdicts) of this host thread
+    ce->begin_frame();
     int64_t R = 0;
-    GeomState geom{};
-    BinState bin{};
-    CapEntry* tile_ce = cap_entry(width, height, true);      // per-size history (capacity, tile-order verdicts) of this host thread
-    if (tile_ce->frames == ~0u) {      // a (re-)used slot must not inherit the previous size's tile-order verdict
-        tile_ce->frames = 0;
-        if (uint32_t* hv = pinned_u32()) hv[R_SLOTS + (int)(tile_ce - g_caps)] = 0u;
-    }
-    tile_ce->frames++;
-    if (tile_ce->boost > 0 && tile_ce->frames - tile_ce->last_overflow > 256u) { tile_ce->boost--; tile_ce->last_overflow = tile_ce->frames; }
-    if (P > 0) {
+    bool blended = false;      // (by the capacity path, which the frame fit)
+    GeomState geom{}; BinState bin{};
+    if (P == 0) {
+        (void)geom_alloc(geom_user, 256);
+        if (int e = alloc_bin(0, 0, false, binning_alloc, binning_user, &bin)) return e;      // (256 B)
+        g_lazy.R = 0;      // (surfel_forward_count of an empty scene)
+    } else {
         // scratch sizes (host-side queries only): [depth-sort scratch | scan state]
         const size_t psort_bytes = align_up(radix_sort_scratch_bytes((size_t)P));
         const size_t temp_bytes = psort_bytes + scan_scratch_words((size_t)P) * sizeof(uint32_t);
@@ -496,10 +625,9 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
         pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = cam_pos;
         pa.rec = geom.rec; pa.depths = geom.depths; pa.depth_keys = geom.dkey_a; pa.ident = geom.ord_a; pa.radii = radii;
         pa.tiles_touched = geom.tiles_touched; pa.clamped = geom.clamped; pa.total_instances = img.total; pa.rects = geom.rects;
-        pa.shjac = (opt_stream && shs != nullptr && M == 16) ? geom.shjac : nullptr;
-        uint32_t* scan_state = reinterpret_cast<uint32_t*>(geom.temp + psort_bytes);
+        pa.shjac = jac ? geom.shjac : nullptr;
         pa.zero_a = reinterpret_cast<uint32_t*>(geom.temp); pa.zero_a_words = (uint32_t)radix_sort_head_words((size_t)P);
-        pa.zero_b = scan_state; pa.zero_b_words = (uint32_t)scan_scratch_words((size_t)P);
+        pa.zero_b = reinterpret_cast<uint32_t*>(geom.temp + psort_bytes); pa.zero_b_words = (uint32_t)scan_scratch_words((size_t)P);
 
         // Binning plan, from history only (nothing of this frame is known on the host yet).
         //  * path: per-tile depth sort (small / medium frames: emit in surfel-index order, order every tile's run by depth afterwards
@@ -508,186 +636,57 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
         //    per tile (unknown on the first call: decided once R has arrived).
         //  * sizes: CAPACITY binning (per-tile path, <= 2^20 instances) sizes the binning buffers from the largest count recent frames
         //    of this size produced and never waits for this frame's count in the middle of the forward (surfel_sort.hip); otherwise
-        //    the buffers are sized exactly, after a host wait for R.
-        const int64_t ntiles_all = (int64_t)gx * gy;
-        constexpr int64_t kTileSortMaxAvg = 640;      // bitonic work grows as n log^2 n: at ~1100 instances per tile it costs 0.25 ms vs 0.15 ms for the P-sized radix sort (C4)
+        //    bin_exact sizes them exactly, after a host wait for R.
         const int end_bit = higher_msb((uint32_t)(gx * gy));
         int per_tile = opt_tile_sort == 2 ? 1 : (opt_tile_sort == 0 ? 0 : -1);
-        if (per_tile < 0 && g_last_R >= 0 && g_last_W == width && g_last_H == height) per_tile = g_last_R <= kTileSortMaxAvg * ntiles_all ? 1 : 0;
-        CapEntry* ce = cap_entry(width, height, true);
-        int64_t cap = 0;
-        if (opt_capacity && per_tile == 1 && ce->maxR >= 0 && debug != 1) {
-            cap = ce->maxR + (ce->maxR >> (3 - ce->boost)) + 4096;
-            cap = (cap + 16383) / 16384 * 16384;      // stable sizes for the caller's caching allocator
-            if (cap > ((int64_t)1 << 20) || !capacity_binning_ok((size_t)cap, end_bit)) cap = 0;
-        }
+        if (per_tile < 0 && g_th.last_R >= 0 && g_th.last_W == width && g_th.last_H == height) per_tile = per_tile_pays(g_th.last_R, gx, gy);
+        const int64_t cap = (opt_capacity && per_tile == 1 && debug != 1) ? ce->capacity(end_bit) : 0;
         if (cap > 0) {      // the binning buffers exist before preprocess runs: it clears the tile sort's head on the way
-            const size_t sort_bytes = capacity_sort_scratch_bytes((size_t)cap, end_bit);
-            size_t bin_bytes = 0;
-            const bool strm = opt_stream && BinState::wants_stream((size_t)cap);
-            BinState::carve(nullptr, (size_t)cap, sort_bytes, &bin_bytes, strm);
-            void* bin_base = binning_alloc(binning_user, bin_bytes);
-            if (!bin_base) return fail(SURFEL_E_ALLOC, "binning buffer allocation failed");
-            bin = BinState::carve(bin_base, (size_t)cap, sort_bytes, nullptr, strm);
+            if (int e = alloc_bin((size_t)cap, capacity_sort_scratch_bytes((size_t)cap, end_bit), opt_stream, binning_alloc, binning_user, &bin)) return e;
             pa.zero_c = reinterpret_cast<uint32_t*>(bin.sort_temp); pa.zero_c_words = (uint32_t)bin_emit_head_words();
             pa.block_totals = geom.offsets;      // (the scan output of the exact path: free here)
         }
-        tm.begin();
-        launch_preprocess_fwd(pa, s);
-        STAGE_END(tm, ST_PRE);
-        // The instance count is copied to the host right behind preprocess.  Exact path: waited for after the depth sort + scan have
-        // been enqueued.  Capacity path: looked at when the whole forward is enqueued (validation only).
+        tm.begin(); launch_preprocess_fwd(pa, s); STAGE_END(tm, ST_PRE);
+        // The instance count goes to the host right behind preprocess.  Capacity path: bin_emit_kernel stores the total into the mapped
+        // pinned buffer itself — no copy kernel; looked at when the whole forward is enqueued (validation only).
         uint32_t* hR = pinned_u32();
         hipEvent_t evR = r_event();
         if (!hR || !evR) return fail(SURFEL_E_HIP, "pinned buffer / event creation failed");
-        const bool host_total = cap > 0;      // capacity path: bin_emit_kernel stores the total into the mapped pinned buffer itself — no copy kernel
-        if (!host_total) {
+        if (cap == 0) {
             HIP_TRY(hipMemcpyAsync(hR, img.total, sizeof(uint32_t) * R_SLOTS, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipEventRecord(evR, s));
-        }
-
-        bool blended = false;
-        if (cap > 0) {
-            const uint32_t* n_dev = img.total + 2 * R_SLOTS;      // written by bin_emit_kernel
-            const bool odd = radix_sort_result_buffer((size_t)cap, 0, end_bit) == 1;
-            uint32_t* va = odd ? bin.vals_alt : bin.point_list;
-            uint32_t* vb = odd ? bin.point_list : bin.vals_alt;
-            tm.begin();
-            launch_bin_emit(P, geom.tiles_touched, geom.rects, geom.offsets, geom.rec, bin.keys_a, va, gx, (size_t)cap, bin.sort_temp, end_bit,
-                            img.total + 2 * R_SLOTS, host_total ? hR + kPinnedTotal : nullptr, s);
-            if (host_total) HIP_TRY(hipEventRecord(evR, s));
-            STAGE_END(tm, ST_EMIT);
-            tm.begin();
-            // the tile ranges come out of the sort's last pass (its scatter knows every key boundary); frames of one tile have no pass
-            const bool fused_ranges = end_bit > 0;
-            const int wk = radix_sort_pairs_u32_devn(bin.keys_a, va, bin.keys_b, vb, (size_t)cap, end_bit, n_dev, bin.sort_temp, fused_ranges ? img.ranges : nullptr, s);
-            STAGE_END(tm, ST_SORT);
-            if (!fused_ranges) {
-                tm.begin();
-                launch_tile_ranges_devn((size_t)cap, n_dev, wk ? bin.keys_b : bin.keys_a, img.ranges, s);
-                STAGE_END(tm, ST_RANGES);
-            }
-            tm.begin();
-            launch_tile_depth_sort(gx * gy, ce->maxR, img.ranges, bin.point_list, geom.dkey_a, bin.vals_alt, bin.keys_a, bin.keys_b, fused_ranges, s);
-            STAGE_END(tm, ST_TSORT);
-            run_tile_order(tile_ce, img.ranges, gx, gy, img.tile_map, img.total + 2 * R_SLOTS + 1, opt_tile_order, s);
-            BlendFwdArgs ba{};
-            ba.W = width; ba.H = height; ba.gx = gx; ba.gy = gy;
-            ba.ranges = img.ranges; ba.point_list = bin.point_list; ba.rec = geom.rec; ba.bg = background;
-            ba.out_color = out_color; ba.out_others = out_others; ba.final_T = img.final_T; ba.n_contrib = img.n_contrib;
-            ba.tile_map = img.tile_map; ba.map_flag = img.total + 2 * R_SLOTS + 1; ba.map_len = map_len;
-            ba.stats = g_blend_stats;
-            ba.strm_rec = bin.strm_rec; ba.strm_mask = bin.strm_mask; ba.totals = img.total; ba.walk_word = img.total + 2 * R_SLOTS + 2;
-            stream_register(bin.point_list, img_base, launch_blend_fwd_writes_stream(ba) ? bin.strm_rec : nullptr, bin.strm_mask, opt_stream && P > 0 && shs != nullptr && M == 16);
-            tm.begin();
-            launch_blend_fwd(ba, s);
-            STAGE_END(tm, ST_BLEND);
+        } else {
+            if (int e = bin_capacity(pa, end_bit, cap, ce->maxR, geom, bin, img, hR, evR, tm, s)) return e;
+            if (int e = blend(ce, width, height, gx, gy, img, img_base, bin, geom.rec, background, out_color, out_others, 0, jac, opt_tile_order, tm, s)) return e;
             if (opt_lazy) {      // the count stays on its way: surfel_forward_count() (or the next forward) collects it
-                g_lazy.pending = true; g_lazy.W = width; g_lazy.H = height; g_lazy.cap = cap; g_lazy.overflowed = false; g_lazy.host_total = host_total;
+                g_lazy.pending = true; g_lazy.W = width; g_lazy.H = height; g_lazy.cap = cap; g_lazy.overflowed = false;
                 if (hipGetDevice(&g_lazy.dev) != hipSuccess) g_lazy.dev = -1;
-                g_last_binning = 4;
+                g_th.last_binning = 4;
                 HIP_TRY(hipGetLastError());
                 return cap;
             }
             HIP_TRY(hipEventSynchronize(evR));      // the emission finished long ago; the device still holds the rest of the forward
-            if (host_total) R = (int64_t)hR[kPinnedTotal];
-            else for (int k = 0; k < R_SLOTS; k++) R += (int64_t)hR[k];
-            g_last_binning = 1;
+            R = pinned_total(hR, true);
             blended = R <= cap;
+            g_th.last_binning = blended ? 1 : 2;
             if (!blended) {      // overflow: the frame is redone with exact sizes below (same results as if it had taken that path at once)
-                g_last_binning = 2;
-                if (ce->boost < 2) ce->boost++;
-                ce->last_overflow = ce->frames;
                 HIP_TRY(hipMemsetAsync(img.ranges, 0, sizeof(uint2) * (size_t)gx * gy, s));
                 // (the capacity path's device total is not this frame's count any more — the exact path leaves 0 there, so that
-                // the backward's overflow guard compares nothing stale; the tile-map flag goes with it, run_tile_order decides again below)
+                // the backward's overflow guard compares nothing stale; the tile-map flag goes with it, run_tile_order decides again in blend)
                 HIP_TRY(hipMemsetAsync(img.total + 2 * R_SLOTS, 0, 2 * sizeof(uint32_t), s));
             }
         }
         if (!blended) {
-            const bool r_known = cap > 0;
-            if (per_tile < 0 && !r_known) {         // first frame of this size: wait for R now (loses the host/device overlap once)
-                HIP_TRY(hipEventSynchronize(evR));
-                int64_t r0 = 0;
-                for (int k = 0; k < R_SLOTS; k++) r0 += (int64_t)hR[k];
-                per_tile = r0 <= kTileSortMaxAvg * ntiles_all ? 1 : 0;
-            }
-            tm.begin();
-            const uint32_t* order = geom.ord_a;      // identity (written by preprocess)
-            if (!per_tile) {
-                // (1) surfel order by view depth (stable; culled surfels carry key 0xffffffff and sort last)
-                const int which = radix_sort_pairs_u32(geom.dkey_a, geom.ord_a, geom.dkey_b, geom.ord_b, (size_t)P, 0, 32, geom.temp, s, true);
-                if (which < 0) return fail(SURFEL_E_LIMIT, "too many surfels for the depth sort");
-                order = which ? geom.ord_b : geom.ord_a;
-            }
-            // (2) instance offsets in emission order: inclusive scan of tiles_touched[order[k]]
-            launch_scan_gather(geom.tiles_touched, order, pa.pack_tiles, geom.offsets, (size_t)P, scan_state, s);
-            STAGE_END(tm, ST_SCAN);
-            if (!r_known) {
-                HIP_TRY(hipEventSynchronize(evR));
-                for (int k = 0; k < R_SLOTS; k++) R += (int64_t)hR[k];
-            }
-
-            const size_t sort_bytes = radix_sort_scratch_bytes((size_t)R);
-            size_t bin_bytes = 0;
-            const bool strm = opt_stream && BinState::wants_stream((size_t)R);
-            BinState::carve(nullptr, (size_t)R, sort_bytes, &bin_bytes, strm);
-            void* bin_base = binning_alloc(binning_user, bin_bytes > 0 ? bin_bytes : 256);
-            if (!bin_base) return fail(SURFEL_E_ALLOC, "binning buffer allocation failed");
-            bin = BinState::carve(bin_base, (size_t)R, sort_bytes, nullptr, strm);
-            if (R > 0) {
-                // (3) stable sort on the tile-id bits only: depth order inside every tile is preserved.  The value buffers
-                // are assigned so that the ping-pong ends in bin.point_list.
-                const bool odd = radix_sort_result_buffer((size_t)R, 0, end_bit) == 1;      // result lands in the b buffers
-                uint32_t* va = odd ? bin.vals_alt : bin.point_list;
-                uint32_t* vb = odd ? bin.point_list : bin.vals_alt;
-                tm.begin();
-                launch_emit_instances(P, geom.rec, geom.rects, order, pa.pack_tiles ? ((1u << PACK_ID_BITS) - 1u) : 0xffffffffu, geom.offsets, bin.keys_a, va, gx, reinterpret_cast<uint32_t*>(bin.sort_temp),
-                                      (uint32_t)radix_sort_head_words((size_t)R), s);
-                STAGE_END(tm, ST_EMIT);
-                tm.begin();
-                const int wk = radix_sort_pairs_u32(bin.keys_a, va, bin.keys_b, vb, (size_t)R, 0, end_bit, bin.sort_temp, s, true);
-                if (wk < 0) return fail(SURFEL_E_LIMIT, "too many tile instances for the tile sort");
-                const uint32_t* sorted_keys = wk ? bin.keys_b : bin.keys_a;
-                STAGE_END(tm, ST_SORT);
-                tm.begin();
-                launch_tile_ranges(R, sorted_keys, img.ranges, s);
-                STAGE_END(tm, ST_RANGES);
-                if (per_tile) {
-                    // (4) every tile orders its run by (depth bits, surfel index); the ping-pong buffers of the tile sort are free now
-                    tm.begin();
-                    launch_tile_depth_sort(gx * gy, R, img.ranges, bin.point_list, geom.dkey_a, bin.vals_alt, bin.keys_a, bin.keys_b, false, s);
-                    STAGE_END(tm, ST_TSORT);
-                }
-            }
+            R = bin_exact(pa, end_bit, per_tile, cap > 0 ? R : -1, geom, &bin, img, hR, evR, opt_stream, binning_alloc, binning_user, tm, s);
+            if (R < 0) return R;
         }
-        g_last_R = R; g_last_W = width; g_last_H = height;
+        ce->record_count(R, cap > 0 && !blended);
         g_lazy.R = R;
-        ce->maxR = R > ce->maxR - ce->maxR / 64 ? R : ce->maxR - ce->maxR / 64;      // the largest recent count, slowly forgotten
-        if (blended) { HIP_TRY(hipGetLastError()); return R; }
-    } else {
-        (void)geom_alloc(geom_user, 256);
-        void* bin_base = binning_alloc(binning_user, 256);
-        if (!bin_base) return fail(SURFEL_E_ALLOC, "binning buffer allocation failed");
-        bin = BinState::carve(bin_base, 0, 0, nullptr);
-        g_lazy.R = 0;      // (surfel_forward_count of an empty scene)
     }
-
-    run_tile_order(tile_ce, img.ranges, gx, gy, img.tile_map, img.total + 2 * R_SLOTS + 1, opt_tile_order, s);
-    BlendFwdArgs ba{};
-    ba.W = width; ba.H = height; ba.gx = gx; ba.gy = gy;
-    ba.ranges = img.ranges; ba.point_list = bin.point_list; ba.rec = geom.rec; ba.bg = background;
-    ba.out_color = out_color; ba.out_others = out_others; ba.final_T = img.final_T; ba.n_contrib = img.n_contrib;
-    ba.tile_map = img.tile_map; ba.map_flag = img.total + 2 * R_SLOTS + 1; ba.map_len = map_len;
-    ba.stats = g_blend_stats;
-    ba.avg_list = (int)(R / ((int64_t)gx * gy));
-    ba.strm_rec = bin.strm_rec; ba.strm_mask = bin.strm_mask; ba.totals = img.total; ba.walk_word = img.total + 2 * R_SLOTS + 2;
-    stream_register(bin.point_list, img_base, launch_blend_fwd_writes_stream(ba) ? bin.strm_rec : nullptr, bin.strm_mask, opt_stream && P > 0 && shs != nullptr && M == 16);
-    tm.begin();
-    launch_blend_fwd(ba, s);
-    STAGE_END(tm, ST_BLEND);
+    if (!blended) {
+        if (int e = blend(ce, width, height, gx, gy, img, img_base, bin, geom.rec, background, out_color, out_others, (int)(R / ((int64_t)gx * gy)), jac, opt_tile_order, tm, s)) return e;
+    }
     HIP_TRY(hipGetLastError());
-    (void)HW;
     return R;
 }
 
@@ -701,7 +700,7 @@ int surfel_rasterize_backward(surfel_alloc_fn scratch_alloc, void* scratch_user,
                               float* dL_dcolors, float* dL_dmeans3D, float* dL_dtransMat, float* dL_dsh, float* dL_dscales,
                               float* dL_drots, int debug, void* stream) {
     (void)tan_fovx; (void)tan_fovy; (void)colors_precomp;
-    g_stage_n = 0;
+    g_th.stage_n = 0;
     const int debug_in = debug;
     const int opt_variant = (debug & SURFEL_OPT_BWD_SCAN) ? 3 : ((debug & SURFEL_OPT_BWD_QUAD) ? 1 : ((debug & SURFEL_OPT_BWD_ROWS) ? 0 : g_opt_bwd_variant));   // 0 rows, 1 quad, 2 auto, 3 scan
     debug &= 0xff;
