@@ -10,7 +10,10 @@ include/surfel_train.h kernels); inputs (parameters, target images, cameras) are
 N > 1: view-parallel — every rank trains on a different view of the same replicated surfel set per step (weak scaling).
 
 Prints ONE JSON line on rank 0 (result_line: at most LINE_MAX characters).  `value` = whole-job training iterations (views) per second.
-Side legs at N = 1: rasterizer-only fwd+bwd, forward-only Msplats/s @1080p (BASELINE metric), CPU baseline (oracle port).
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+everything else: the box probe, the window census behind `roofline` / `step_roofline`, at N = 1 the side legs (other workloads,
+rasterizer-only fwd+bwd, forward-only Msplats/s @1080p (BASELINE metric), the config-3 full train, CPU baselines), at N > 1 the
+standalone collectives and the C4 scaling line.
 """
 import argparse
 import json
@@ -225,7 +228,7 @@ def _rehearse_spawn(args):
     return 0
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -243,7 +246,12 @@ def main():
     ap.add_argument("--no-legs", action="store_true", help="skip the extra N = 1 workload legs (C4-synthetic, heavy-footprint C2H, trained state)")
     ap.add_argument("--no-full-train", action="store_true", help="skip the config-3 full-train leg (30 000 iterations of the reference schedule, ~30 - 60 s)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the 1080p forward sweep over P = 0.3 ... 10 M surfels")
-    ap.add_argument("--quick", action="store_true", help="headline leg only (= --no-legs --no-cpu-baseline --no-1080p --no-raster-only)")
+    ap.add_argument("--quick", action="store_true", help="headline leg only (= --no-legs --no-cpu-baseline --no-1080p --no-raster-only --no-full-train "
+                                                         "--no-sweep); with --full: the box probe, census and rooflines of the headline leg, no side legs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline: the box probe, the window census and its rooflines, the side legs and "
+                         "CPU baselines (N = 1), the standalone collectives and the C4 scaling line (N > 1); the --no-* options, --quick and --legs "
+                         "choose among them.  Off: set-up, warm-up, the timed steps, --dump-outputs and the result line only")
     ap.add_argument("--sharding", choices=("views", "bands"), default="views",
                     help="N > 1: 'views' = one view per GPU per iteration (weak scaling, default); 'bands' = tile-band sharding of ONE view "
                          "per iteration across the GPUs (strong scaling; BASELINE config 5: --workload C5)")
@@ -254,12 +262,19 @@ def main():
                          "updated parameters, Adam moments and densification statistics) as DIR/<name>.npy")
     ap.add_argument("--detail-json", metavar="PATH", default=None,
                     help="also write the full result object (every side leg in full) to PATH; stdout gets the compact line")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.quick or not args.full:
+        args.no_legs = args.no_cpu_baseline = args.no_1080p = args.no_raster_only = args.no_full_train = args.no_sweep = True
+    if not args.full:
+        args.no_scale_leg = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # ---- launch contract: `python bench.py --gpus N` run DIRECTLY must time N ranks.  Without a torch.distributed.run
     # environment this process re-executes itself under it (one rank per GPU, rendezvous on 127.0.0.1) and relays the result.
-    if args.quick:
-        args.no_legs = args.no_cpu_baseline = args.no_1080p = args.no_raster_only = args.no_full_train = args.no_sweep = True
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             raise SystemExit(_respawn(args.gpus))
@@ -305,7 +320,7 @@ def main():
     # what this box sustains, in this process, BEFORE the set-up iterations (helpers_bench.box_probe; its host-side parts leave the GPU idle for
     # tens of milliseconds: placed between the set-up iterations and the warm-up it cost the 20-step window 3 % — clocks)
     probe = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from helpers_bench import box_probe
             probe = box_probe(dev)
@@ -359,7 +374,7 @@ def main():
     tr.time_exchange = False
     wire = dict(tr.wire)
     coll_us = None
-    if world > 1 and args.sharding == "views" and backend == "nccl":
+    if args.full and world > 1 and args.sharding == "views" and backend == "nccl":
         # the two collectives of the step on their real buffers, back to back and alone on the device: what the exchange costs when
         # NOTHING hides it (exposed_ms_per_step above is what was not hidden in the timed region)
         try:      # (an extra: must never cost the run its headline)
@@ -387,9 +402,11 @@ def main():
     # per-stage breakdown of the rasterizer + the window's instance counts: a second, untimed pass over the SAME frames (same view order)
     # with every stage bracketed by events (bracketing all ~9 stages costs ~10 us each: not inside the timed region) and R / Rs / V read
     # back per frame -> the roofline's bytes and the kernel times belong to the same frames
-    stages, census = window_census(tr, args.steps, W, H)
-    fence()
-    stages.update(dom_stage)      # the dominant kernel's duration: the one measured inside the timed window
+    census = None
+    if args.full:
+        stages, census = window_census(tr, args.steps, W, H)
+        fence()
+        stages.update(dom_stage)      # the dominant kernel's duration: the one measured inside the timed window
     cpu_snapshot = snapshot_for_cpu(tr) if (rank == 0 and world == 1 and trained_info and not args.no_cpu_baseline) else None
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -397,7 +414,7 @@ def main():
         dt = float(tt.item())
 
     # ---- workload statistics for the roofline (P, V, R, n_pass): means over the window's frames
-    V, R, Rs = census["V"], census["R"], census["Rs"]
+    V, R, Rs = (census["V"], census["R"], census["Rs"]) if census else (None, None, None)
     tiles = ((W + 15) // 16) * ((H + 15) // 16)
     n_pass = -(-(32 + max(1, (tiles - 1).bit_length())) // 8)
 
@@ -406,7 +423,7 @@ def main():
         ms_per_step = dt / args.steps * 1e3
         bands = world > 1 and args.sharding == "bands"
         iters_per_s = (1 if bands else world) * args.steps / dt
-        per_kernel = {k: v[0] / v[1] for k, v in stages.items()}
+        per_kernel = {k: v[0] / v[1] for k, v in stages.items()} if census else {}      # (empty: no roofline objects)
         roof = roofline_object(per_kernel, args.workload, P, V, R, Rs, W, H, n_pass)
         if roof:
             roof["window"] = census
@@ -431,8 +448,9 @@ def main():
                                       "surfels, %s, lambda_dssim 0.2, lambda_normal 0.05, lambda_dist 1000, depth_ratio 1, "
                                       "Adam on 58 floats/surfel; %d set-up iterations before the warm-up" % (args.workload, P, W, H, n_views,
                                       "1 view/iteration split into row bands" if bands else "1 view/GPU/iteration", PRIME),
-                          "P": P, "image": "%dx%d" % (W, H), "visible_mean": round(V, 1), "instances_R_mean": round(R, 1), "instances_staged_mean": round(Rs, 1),
-                          "instances_R_range": [census["R_min"], census["R_max"]], "n_pass": n_pass, "tiles": tiles,
+                          "P": P, "image": "%dx%d" % (W, H),
+                          **({"visible_mean": round(V, 1), "instances_R_mean": round(R, 1), "instances_staged_mean": round(Rs, 1),
+                              "instances_R_range": [census["R_min"], census["R_max"]]} if census else {}), "n_pass": n_pass, "tiles": tiles,
                           "trained_state": trained_info,
                           "parallelism": ("tile-band sharding of one view over %d GPUs (image bands all-gathered, same gradient exchange)" % world) if bands
                           else ("view-parallel dp%d; per iteration 1 all-reduce of 40 B/surfel (geometry gradients) + 1 all-gather of "

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""A/B of whole libraries (and option settings) on one GPU box: every (library, SURFEL_OPTIONS) arm runs `bench.py --workload W --quick` in
+"""A/B of whole libraries (and option settings) on one GPU box: every (library, SURFEL_OPTIONS) arm runs `bench.py --workload W --full --quick` in
 its own process, arms interleaved and repeated, trained states shared through /tmp/state_<W>.ply.
     python scripts/ab_libs.py "C2,trained,garden" 2 name=lib_tag[:opt=val,...] ...      (lib_tag "" = the product library)
 Prints one JSON line per (workload, arm): ms_per_step and the blend kernels' event times, min / median over the repeats."""
@@ -28,7 +28,7 @@ def main():
                     env["SURFEL_LIB"] = os.path.join(REPO, "2d-gaussian-splatting_amd", "lib", "libsurfel_hip_%s.so" % tag)
                 if opts:
                     env["SURFEL_OPTIONS"] = opts
-                p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", wl, "--quick", "--steps", "40", "--warmup", "10"] + state,
+                p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", wl, "--full", "--quick", "--steps", "40", "--warmup", "10"] + state,
                                    capture_output=True, text=True, timeout=900, env=env)
                 lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
                 if not lines:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run ON THE GPU BOX from the repo root (via gpurun):  bash scripts/profile_gpu.sh <tag> [workload] [full|short]
 # Produces under gpurun_out/prof_<tag>_<workload>/ :
-#   kt/      rocprofv3 --kernel-trace --stats of `python bench.py --workload <workload> --quick` (timed training step only: side legs off,
+#   kt/      rocprofv3 --kernel-trace --stats of `python bench.py --workload <workload> --full --quick` (timed training step only: side legs off,
 #            so the per-kernel averages are those of the timed region)
 #   fetch/   --pmc FETCH_SIZE   (own pass: FETCH_SIZE takes 3 of the 4 TCC slots)
 #   write/   --pmc WRITE_SIZE   (own pass)
@@ -24,9 +24,9 @@ export SURFEL_OPTIONS="bwd_variant=$WALK"
 echo "$WALK" > $OUT/walk.txt
 STATE=""
 case $WL in trained|garden) STATE="--state /tmp/state_$WL.ply"; timeout 200 python $ROOT/bench.py --workload $WL $STATE --quick --steps 2 --warmup 1 > $OUT/bench_make_state.log 2>&1;; esac
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $ROOT/bench.py --workload $WL $STATE --quick > $OUT/bench_kt.log 2>&1
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $ROOT/bench.py --workload $WL $STATE --full --quick > $OUT/bench_kt.log 2>&1
 # (the PMC passes time the same views as the bench leg of this workload: same steps / warm-up, the window reseeds its view order)
-case $WL in trained) SHORT="--workload $WL $STATE --steps 30 --warmup 5 --quick";; garden|C4|C2H) SHORT="--workload $WL $STATE --steps 20 --warmup 5 --quick";; *) SHORT="--workload $WL $STATE --steps 20 --warmup 5 --quick";; esac
+case $WL in trained) SHORT="--workload $WL $STATE --steps 30 --warmup 5 --full --quick";; garden|C4|C2H) SHORT="--workload $WL $STATE --steps 20 --warmup 5 --full --quick";; *) SHORT="--workload $WL $STATE --steps 20 --warmup 5 --full --quick";; esac
 timeout 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o p -- python $ROOT/bench.py $SHORT > $OUT/bench_fetch.log 2>&1
 timeout 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o p -- python $ROOT/bench.py $SHORT > $OUT/bench_write.log 2>&1
 timeout 200 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT \

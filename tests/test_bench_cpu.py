@@ -89,3 +89,19 @@ def test_dump_outputs_sample_is_seeded_and_bounded(tmp_path):
     xyz = _views(m.theta, P)["xyz"].numpy()
     assert params.shape == (len(idx), FLOATS) and SECTIONS[0][0] == "xyz" and np.array_equal(params[:, :3], xyz[idx])
     assert np.array_equal(np.load(tmp_path / "a" / "radii.npy"), tr.last["radii"].numpy()[idx].astype(np.float32))
+
+
+def test_plain_run_leaves_every_extra_to_full():
+    """A plain run is set-up, warm-up, the timed steps and the line: every side leg is off unless --full; under --full, --quick and the
+    --no-* options pick among them as before."""
+    sys.path.insert(0, REPO)
+    import bench
+    extras = ("no_legs", "no_cpu_baseline", "no_1080p", "no_raster_only", "no_full_train", "no_sweep", "no_scale_leg")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not plain.full and all(getattr(plain, k) for k in extras) and (plain.gpus, plain.steps, plain.warmup) == (1, 7, 3)
+    full = bench.parse_args(["--full"])
+    assert full.full and not any(getattr(full, k) for k in extras)
+    quick = bench.parse_args(["--full", "--quick"])
+    assert quick.full and all(getattr(quick, k) for k in extras if k != "no_scale_leg") and not quick.no_scale_leg
+    some = bench.parse_args(["--full", "--no-sweep"])
+    assert some.no_sweep and not any(getattr(some, k) for k in extras if k != "no_sweep")
