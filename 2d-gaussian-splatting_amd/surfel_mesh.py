@@ -1,10 +1,11 @@
-"""Bounded TSDF mesh extraction on MI355X — the reference's `GaussianExtractor` bounded path and `post_process_mesh`
-(utils/mesh_utils.py:22-181) and the mesh step of render.py:86-106, without Open3D.
+"""TSDF mesh extraction on MI355X — the reference's `GaussianExtractor` (bounded and unbounded paths) and `post_process_mesh`
+(utils/mesh_utils.py:22-280) and the mesh step of render.py:86-106, without Open3D, scikit-image or trimesh.
 
 The fusion, marching cubes and the connected-component filter are HIP kernels of libsurfel_hip.so (include/surfel_mesh.h); the
-rules they follow are written down in MESH.md.  Maps stay on the device; only counts cross to the host.
+rules they follow are written down in MESH.md.  Maps stay on the device; only counts cross to the host.  The unbounded path's
+kernels sit behind include/surfel_mesh_unbounded.h.
 
-    python 2d-gaussian-splatting_amd/surfel_mesh.py -m MODEL_DIR [--iteration N] [--mesh_res 1024] ...
+    python 2d-gaussian-splatting_amd/surfel_mesh.py -m MODEL_DIR [--iteration N] [--mesh_res 1024] [--unbounded] ...
 """
 import argparse
 import ctypes as C
@@ -204,6 +205,104 @@ def prepare_view(surf_depth, rgb, mask, depth_trunc):
     return dout, rgba
 
 
+# ------------------------------------------------------------------------------------------------ unbounded (MESH.md §Unbounded)
+def contract(x):
+    """utils/mesh_utils.py:189-191: x where |x| < 1, else (2 - 1/|x|) x/|x| (last axis)."""
+    mag = torch.linalg.norm(x, ord=2, dim=-1)[..., None]
+    return torch.where(mag < 1, x, (2 - (1 / mag)) * (x / mag))
+
+
+def uncontract(y):
+    """utils/mesh_utils.py:193-195: y where |y| < 1, else y / (|y| (2 - |y|))."""
+    mag = torch.linalg.norm(y, ord=2, dim=-1)[..., None]
+    return torch.where(mag < 1, y, (1 / (2 - mag) * (y / mag)))
+
+
+def lattice_size(resolution):
+    """Distinct samples per axis of the reference's resolution/512 crops of 512 linspace samples: neighbouring crops share a plane."""
+    return (int(resolution) // 512) * 511 + 1
+
+
+def lattice_half_width(xyz, center, radius):
+    """R = min(quantile_0.95 |contract((xyz - center) / radius)| + 0.01, 1.9) (mesh_utils.py:263-265; numpy's linear quantile)."""
+    r = contract((xyz.detach().float() - center) / radius).norm(dim=-1).cpu().numpy()
+    return min(float(np.quantile(r, q=0.95)) + 0.01, 1.9)
+
+
+def pack_views(projs, depths, rgbs=None):
+    """(views uint8 [64 n] on the device = surfel_unbounded_view[n], packed depth, packed rgb or None).  projs: full_proj_transform
+    [4,4] per view (row-vector convention); depths [H,W] or [1,H,W]; rgbs [3,H,W]."""
+    dev = depths[0].device
+    arr = (_n.UnboundedView * len(depths))()
+    off = 0
+    for k, (P, d) in enumerate(zip(projs, depths)):
+        P = np.asarray(P.detach().cpu().numpy() if torch.is_tensor(P) else P, np.float32)
+        H, W = d.shape[-2:]
+        arr[k].proj[:] = [float(x) for x in np.concatenate([P[:, 0], P[:, 1], P[:, 3]])]
+        arr[k].H, arr[k].W, arr[k].offset = int(H), int(W), off
+        off += int(H) * int(W)
+    views = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    depth = torch.cat([d.detach().float().reshape(-1) for d in depths])
+    rgb = None if rgbs is None else torch.cat([c.detach().float().reshape(-1) for c in rgbs])
+    return views, depth, rgb
+
+
+class UnboundedLattice:
+    """The M^3 contracted lattice through the library (include/surfel_mesh_unbounded.h).  `budget_bytes` bounds the lattice, the
+    slab scratch and the outputs; MeshLimitError is raised before anything is allocated for them."""
+
+    def __init__(self, M, R, center, radius, voxel_size, budget_bytes, device, slab=0):
+        self.lib, self.device = _n.load(), torch.device(device)
+        self.alloc = _n.TorchAllocator(self.device)
+        self.v = _n.UnboundedVolume()
+        self.v.M, self.v.slab, self.v.R = int(M), int(slab), float(R)
+        self.v.center[:] = [float(x) for x in np.asarray(center.detach().cpu().numpy() if torch.is_tensor(center) else center, np.float64)]
+        self.v.radius, self.v.voxel_size, self.v.budget_bytes = float(radius), float(voxel_size), int(budget_bytes)
+        self._call("surfel_unbounded_init", self.lib.surfel_unbounded_init, C.byref(self.v), self.alloc.cb, None, self._s())
+
+    def _s(self):
+        return _n.current_stream_ptr(self.device)
+
+    def _call(self, what, fn, *args):
+        with torch.cuda.device(self.device):
+            rc = fn(*args)
+        if rc == -4:
+            raise MeshLimitError("%s: %s" % (what, _n.last_error()))
+        return _check(rc, what)
+
+    def fuse(self, views, depth, count=None):
+        """views / depth from pack_views; count: a uint16-sized tensor [M^3] (int16 storage) that receives every sample's view count."""
+        n = views.numel() // 64
+        self._call("surfel_unbounded_fuse", self.lib.surfel_unbounded_fuse, C.byref(self.v), n, _n.ptr(views), _n.ptr(depth), _n.ptr(count), self._s())
+
+    def tsdf(self):
+        """The lattice [M, M, M] indexed [z, y, x] (a view of the library's buffer)."""
+        M = self.v.M
+        for t in self.alloc.held:
+            if t.data_ptr() == self.v.tsdf:
+                return t[:4 * M ** 3].view(torch.float32).view(M, M, M)
+        raise KeyError("tsdf")
+
+    def extract(self):
+        """(verts [V,3] world, clipped to +-32, tris [F,3] int32) in lattice / cube order."""
+        self._call("surfel_unbounded_count", self.lib.surfel_unbounded_count, C.byref(self.v), self._s())
+        V, F = int(self.v.nverts), int(self.v.ntris)
+        verts = torch.empty((V, 3), dtype=torch.float32, device=self.device)
+        tris = torch.empty((F, 3), dtype=torch.int32, device=self.device)
+        self._call("surfel_unbounded_extract", self.lib.surfel_unbounded_extract, C.byref(self.v), _n.ptr(verts), _n.ptr(tris), self._s())
+        return verts, tris
+
+
+def color_vertices(verts, views, depth, rgb, sdf_trunc):
+    """colors [V,3] = sum of bilinear rgb / (1 + n) over the views that see a vertex within sdf_trunc (surfel_unbounded_color)."""
+    V = int(verts.shape[0])
+    cols = torch.empty((V, 3), dtype=torch.float32, device=verts.device)
+    with torch.cuda.device(verts.device):
+        _check(_n.load().surfel_unbounded_color(V, _n.ptr(verts.contiguous()), views.numel() // 64, _n.ptr(views), _n.ptr(depth), _n.ptr(rgb),
+                                                float(sdf_trunc), _n.ptr(cols), _n.current_stream_ptr(verts.device)), "surfel_unbounded_color")
+    return cols
+
+
 # ------------------------------------------------------------------------------------------------ the reference's interface
 DEFAULT_BUDGET = 64 << 30
 
@@ -261,6 +360,30 @@ class GaussianExtractor:
         self.volume = vol
         return mesh
 
+    @torch.no_grad()
+    def extract_mesh_unbounded(self, resolution=1024, slab=0):
+        """Contracted-lattice fusion and marching cubes (MESH.md §Unbounded, utils/mesh_utils.py:184-280).  resolution must be a
+        multiple of 512; the lattice holds (resolution/512) * 511 + 1 samples per axis.  Returns a TriangleMesh on the device."""
+        if resolution <= 0 or resolution % 512 != 0:
+            raise ValueError("extract_mesh_unbounded: resolution must be a positive multiple of 512, got %r" % (resolution,))
+        dev = self.background.device
+        M = lattice_size(resolution)
+        voxel_size = self.radius * 2 / resolution
+        R = lattice_half_width(self.gaussians.get_xyz, self.center, self.radius)
+        print("Computing sdf grid resolution %d x %d x %d (lattice %d^3, half-width %.4f)" % (resolution, resolution, resolution, M, R))
+        print("Define the voxel_size as %g" % voxel_size)
+        lat = UnboundedLattice(M, R, self.center, self.radius, voxel_size, self.budget_bytes, dev, slab=slab)
+        t = _Timer(self.timings, dev)
+        views, depth, rgb = pack_views([c.full_proj_transform for c in self.viewpoint_stack], self.depthmaps, self.rgbmaps)
+        lat.fuse(views, depth)
+        t.lap("fuse")
+        verts, tris = lat.extract()
+        t.lap("extract")
+        cols = color_vertices(verts, views, depth, rgb, 5 * voxel_size)
+        t.lap("color")
+        self.lattice = lat
+        return TriangleMesh(verts, tris, cols)
+
 
 def cluster_triangles(mesh):
     """(label [F] = smallest triangle id of the triangle's edge-connected cluster, size [F] = triangles per label id)."""
@@ -310,7 +433,7 @@ def _latest_iteration(model_dir):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Bounded TSDF mesh of a trained model (render.py's mesh step). Unlike the reference, which "
+    ap = argparse.ArgumentParser(description="TSDF mesh of a trained model (render.py's mesh step), bounded or --unbounded. Unlike the reference, which "
                                              "fuses only the training split, every camera in cameras.json is fused.")
     ap.add_argument("-m", "--model_path", required=True)
     ap.add_argument("--iteration", default=-1, type=int)
@@ -321,6 +444,7 @@ def main(argv=None):
     ap.add_argument("--mesh_res", default=1024, type=int, help="Mesh: resolution for unbounded mesh extraction")
     ap.add_argument("--depth_ratio", default=0.0, type=float)
     ap.add_argument("--white_background", action="store_true")
+    ap.add_argument("--unbounded", action="store_true", help="Mesh: unbounded mode (contracted lattice of mesh_res, a multiple of 512)")
     ap.add_argument("--budget_gb", default=DEFAULT_BUDGET / 2 ** 30, type=float, help="byte budget of the TSDF volume (GiB)")
     args = ap.parse_args(argv)
     import surfel_io
@@ -338,15 +462,20 @@ def main(argv=None):
     os.makedirs(out, exist_ok=True)
     gaussians.active_sh_degree = 0      # render.py:91: diffuse colour only
     ext.reconstruction(cams)
-    depth_trunc = ext.radius * 2.0 if args.depth_trunc < 0 else args.depth_trunc
-    voxel_size = depth_trunc / args.mesh_res if args.voxel_size < 0 else args.voxel_size
-    sdf_trunc = 5.0 * voxel_size if args.sdf_trunc < 0 else args.sdf_trunc
-    mesh = ext.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc)
-    surfel_io.write_triangle_mesh(os.path.join(out, "fuse.ply"), mesh)
-    print("mesh saved at {}".format(os.path.join(out, "fuse.ply")))
+    if args.unbounded:
+        name = "fuse_unbounded.ply"
+        mesh = ext.extract_mesh_unbounded(resolution=args.mesh_res)
+    else:
+        name = "fuse.ply"
+        depth_trunc = ext.radius * 2.0 if args.depth_trunc < 0 else args.depth_trunc
+        voxel_size = depth_trunc / args.mesh_res if args.voxel_size < 0 else args.voxel_size
+        sdf_trunc = 5.0 * voxel_size if args.sdf_trunc < 0 else args.sdf_trunc
+        mesh = ext.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc)
+    surfel_io.write_triangle_mesh(os.path.join(out, name), mesh)
+    print("mesh saved at {}".format(os.path.join(out, name)))
     post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
-    surfel_io.write_triangle_mesh(os.path.join(out, "fuse_post.ply"), post)
-    print("mesh post processed saved at {}".format(os.path.join(out, "fuse_post.ply")))
+    surfel_io.write_triangle_mesh(os.path.join(out, name.replace(".ply", "_post.ply")), post)
+    print("mesh post processed saved at {}".format(os.path.join(out, name.replace(".ply", "_post.ply"))))
     return 0
 
 

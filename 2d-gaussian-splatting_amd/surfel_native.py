@@ -27,6 +27,9 @@ EXPORTS = ["surfel_abi_version", "surfel_last_error", "surfel_rasterize_forward"
 # include/surfel_mesh.h
 MESH_EXPORTS = ["surfel_tsdf_table_bytes", "surfel_tsdf_block_bytes", "surfel_mesh_prepare_view", "surfel_tsdf_init", "surfel_tsdf_mark", "surfel_tsdf_allocate",
                 "surfel_tsdf_integrate", "surfel_tsdf_count", "surfel_tsdf_extract", "surfel_mesh_clusters", "surfel_mesh_filter"]
+# include/surfel_mesh_unbounded.h
+UNBOUNDED_EXPORTS = ["surfel_unbounded_bytes", "surfel_unbounded_init", "surfel_unbounded_fuse", "surfel_unbounded_count", "surfel_unbounded_extract",
+                     "surfel_unbounded_color"]
 
 # per-call option overrides carried in the upper bits of the `debug` argument (include/surfel_hip.h)
 OPT_NO_CULL = 1 << 8
@@ -60,6 +63,18 @@ class TsdfVolume(C.Structure):
                 ("table", C.c_void_p), ("scratch", C.c_void_p), ("nblocks", C.c_int64), ("keys", C.c_void_p), ("stamp", C.c_void_p),
                 ("list", C.c_void_p), ("tsdf_rgb", C.c_void_p), ("weight", C.c_void_p), ("info", C.c_void_p), ("vbase", C.c_void_p),
                 ("tbase", C.c_void_p), ("pool_scratch", C.c_void_p), ("views", C.c_int64), ("nverts", C.c_int64), ("ntris", C.c_int64)]
+
+
+class UnboundedVolume(C.Structure):
+    """surfel_unbounded_volume of include/surfel_mesh_unbounded.h"""
+    _fields_ = [("M", C.c_int), ("slab", C.c_int), ("R", C.c_float), ("center", C.c_float * 3), ("radius", C.c_float), ("voxel_size", C.c_float),
+                ("budget_bytes", C.c_int64), ("tsdf", C.c_void_p), ("info", C.c_void_p), ("vbase", C.c_void_p), ("tbase", C.c_void_p),
+                ("scan_scratch", C.c_void_p), ("slab_base", C.c_void_p), ("nslabs", C.c_int64), ("nverts", C.c_int64), ("ntris", C.c_int64)]
+
+
+class UnboundedView(C.Structure):
+    """surfel_unbounded_view of include/surfel_mesh_unbounded.h (64 B; an array of them is copied to the device)"""
+    _fields_ = [("proj", C.c_float * 12), ("H", C.c_int32), ("W", C.c_int32), ("offset", C.c_int64)]
 
 
 _lib = None
@@ -145,6 +160,17 @@ def load():
                                 ("surfel_tsdf_extract", i, [vol, vp, vp, vp, vp]),
                                 ("surfel_mesh_clusters", i, [ALLOC_FN, vp, i64, i64, vp, vp, vp, vp]),
                                 ("surfel_mesh_filter", i, [ALLOC_FN, vp, i64, i64, vp, vp, vp, vp, vp, i, vp, vp, vp, C.POINTER(C.c_int64), vp])):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        # ---- include/surfel_mesh_unbounded.h
+        uvol = C.POINTER(UnboundedVolume)
+        for name, res, args in (("surfel_unbounded_bytes", i64, [uvol]),
+                                ("surfel_unbounded_init", i, [uvol, ALLOC_FN, vp, vp]),
+                                ("surfel_unbounded_fuse", i, [uvol, i, vp, vp, vp, vp]),
+                                ("surfel_unbounded_count", i, [uvol, vp]),
+                                ("surfel_unbounded_extract", i, [uvol, vp, vp, vp]),
+                                ("surfel_unbounded_color", i, [i64, vp, i, vp, vp, vp, f, vp, vp])):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

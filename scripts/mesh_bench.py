@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """Timing of the bounded TSDF mesh extraction (MESH.md) on trained states: one JSON line per (state, mesh_res).
 
-    python scripts/mesh_bench.py [--states trained,garden] [--res 512,1024] [--garden-state PATH.ply] [--model-dir DIR]
+    python scripts/mesh_bench.py [--states trained,garden] [--res 512,1024] [--garden-state PATH.ply] [--model-dir DIR] [--unbounded]
 
 Every stage is timed with a device synchronisation around it: render (every view through render()), touch (allocation passes and
 pool allocation), integrate (touch lists + fusion of every view), extract (counts, scans, emission), clusters (post_process_mesh).
 --model-dir: also writes the `trained` state as a model directory the CLI reads (point_cloud/iteration_N/point_cloud.ply +
 cameras.json) so that `surfel_mesh.py -m DIR` can be run on it.
+--unbounded: the unbounded extraction (MESH.md §Unbounded) at resolution N = res instead: render, fuse (view packing + lattice
+fusion), extract (both slab sweeps), color, clusters; M, V, F and the fusion's sample-views per second.
 """
 import argparse
 import json
@@ -84,6 +86,36 @@ def _run(dev, name, model, cams, res, quiet=False):
     return ext, mesh, post
 
 
+def run_unbounded(dev, name, model, cams, res, repeat=2):
+    """`repeat` extractions; the line reports the last."""
+    import surfel_mesh
+    from surfel_render import render
+    import surfel_trainer as TR
+    for k in range(repeat):
+        timings = {}
+        ext = surfel_mesh.GaussianExtractor(model, render, TR.pipeline_params(depth_ratio=0.0))
+        ext.timings = timings
+        sh = model.active_sh_degree
+        model.active_sh_degree = 0
+        ext.reconstruction(cams)
+        mesh = ext.extract_mesh_unbounded(res)
+        torch.cuda.synchronize(dev); t0 = time.perf_counter()
+        post = surfel_mesh.post_process_mesh(mesh, 50)
+        torch.cuda.synchronize(dev)
+        timings["clusters"] = (time.perf_counter() - t0) * 1e3
+        model.active_sh_degree = sh
+        M = int(ext.lattice.v.M)
+        line = {"state": name, "mode": "unbounded", "resolution": res, "M": M, "R": round(float(ext.lattice.v.R), 5), "views": len(cams),
+                "image": [cams[0].image_width, cams[0].image_height], "slabs": int(ext.lattice.v.nslabs),
+                "V": int(mesh.vertices.shape[0]), "F": int(mesh.triangles.shape[0]),
+                "V_post": int(post.vertices.shape[0]), "F_post": int(post.triangles.shape[0]),
+                "ms": {k_: round(x, 2) for k_, x in timings.items()},
+                "fuse_sample_views_per_s": float("%.4g" % (M ** 3 * len(cams) / (timings["fuse"] * 1e-3)))}
+        del ext, mesh, post
+        torch.cuda.empty_cache()
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--states", default="trained,garden")
@@ -91,6 +123,7 @@ def main():
     ap.add_argument("--garden-state", default=None, help="cached garden .ply (trained once, then loaded)")
     ap.add_argument("--trained-state", default=None, help="cached trained .ply")
     ap.add_argument("--model-dir", default=None)
+    ap.add_argument("--unbounded", action="store_true", help="time extract_mesh_unbounded (res = resolution N, a multiple of 512)")
     args = ap.parse_args()
     import helpers_bench as HB
     dev = torch.device("cuda:0")
@@ -100,7 +133,7 @@ def main():
         if args.model_dir and name == "trained":
             write_model_dir(model, train_cams, args.model_dir, 6000)
         for res in (int(r) for r in args.res.split(",")):
-            run(dev, name, model, train_cams, res)
+            (run_unbounded if args.unbounded else run)(dev, name, model, train_cams, res)
         del model
         torch.cuda.empty_cache()
 
