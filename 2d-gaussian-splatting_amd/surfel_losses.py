@@ -5,8 +5,6 @@ Same names, argument meaning and return shapes; the work is done by two LDS-tile
 (include/surfel_train.h) instead of five grouped conv2d calls + ~40 elementwise kernels per iteration.
 No CPU / PyTorch fallback: CPU tensors raise.
 """
-import os
-
 import torch
 
 import surfel_native as _n
@@ -179,9 +177,58 @@ def photometric_loss(image, gt_image, lambda_dssim=0.2):
     return _PhotometricLoss.apply(image, gt_image, lambda_dssim)
 
 
-# the two halves of the training loss (L1 + SSIM | allmap regularisers) in one launch per direction (csrc/train_fused.hip); 0: separate
-# launches — same kernels' bodies, same bits (tests/test_gpu_train.py::test_fused_loss_launches_keep_the_bits)
-FUSED_LOSS = os.environ.get("SURFEL_FUSED_LOSS", "1") != "0"
+# the two halves of the training loss (L1 + SSIM | allmap regularisers) in one launch per direction (csrc/train_fused.hip); False:
+# separate launches — same kernels' bodies, same bits (tests/test_gpu_train.py::test_fused_loss_launches_keep_the_bits)
+FUSED_LOSS = True
+
+
+def _loss_forward(lib, planes, H, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg, s):
+    """L1 + SSIM partial sums into `partials` [+ the regularisers' per-16x16-block sums]; returns (allmap as fp32, those sums) or
+    (None, None) without regularisers.  Both halves in one launch where FUSED_LOSS allows: they share no data, their workgroups run
+    side by side."""
+    am = pb = None
+    if reg:
+        am = allmap.detach().contiguous().float()
+        pb = torch.empty((((W + 15) // 16) * ((H + 15) // 16), 2), dtype=torch.float32, device=x.device)
+    if reg and planes == 3 and FUSED_LOSS:
+        _check(lib.surfel_train_loss_forward(H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), _n.ptr(am), _n.ptr(cam),
+                                             float(depth_ratio), _n.ptr(pb), s), "surfel_train_loss_forward")
+    else:
+        _check(lib.surfel_l1_ssim_forward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), s), "surfel_l1_ssim_forward")
+        if reg:
+            # maps = NULL: only the two regulariser sums are needed (the backward recomputes from allmap)
+            _check(lib.surfel_render_post_forward(H, W, _n.ptr(am), _n.ptr(cam), float(depth_ratio), None, _n.ptr(pb), s),
+                   "surfel_render_post_forward")
+    return am, pb
+
+
+def _loss_backward(lib, planes, H, W, x, y, dmaps, am, cam, ratio, weights, g, fin, s):
+    """dL/dimage and dL/dallmap (None without regularisers: am is None) for the loss weights (L1, SSIM, normal, distortion) of
+    the pixel means, scaled by the upstream scalar g.  fin = (partials, regulariser sums, lambda_dssim, lambda_normal,
+    lambda_dist, scalars out, total out): the fused launch's optional finalize workgroup (null pointers: none)."""
+    w_l1, w_ssim, w_n, w_d = weights
+    grad_img = torch.empty_like(x)
+    grad_am = None if am is None else torch.empty_like(am)
+    if am is not None and planes == 3 and FUSED_LOSS:
+        _check(lib.surfel_train_loss_backward(H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), w_l1, w_ssim, _n.ptr(am), _n.ptr(cam), ratio, w_n, w_d,
+                                              _n.ptr(g), _n.ptr(grad_img), _n.ptr(grad_am), _n.ptr(fin[0]), _n.ptr(fin[1]), fin[2], fin[3], fin[4],
+                                              _n.ptr(fin[5]), _n.ptr(fin[6]), s), "surfel_train_loss_backward")
+    else:
+        _check(lib.surfel_l1_ssim_backward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), w_l1, w_ssim, _n.ptr(g), _n.ptr(g),
+                                           _n.ptr(grad_img), s), "surfel_l1_ssim_backward")
+        if am is not None:
+            _check(lib.surfel_render_post_backward(H, W, _n.ptr(am), _n.ptr(cam), ratio, None, w_n, w_d, _n.ptr(g), _n.ptr(grad_am), s),
+                   "surfel_render_post_backward")
+    return grad_img, grad_am
+
+
+def _regulariser_inputs(image, allmap, cam_consts, lambda_normal, lambda_dist):
+    """(allmap, cam_consts) as the loss Functions take them: no camera constants = no regularisers (then both weights must be 0)."""
+    if cam_consts is not None:
+        return allmap, cam_consts
+    if lambda_normal != 0.0 or lambda_dist != 0.0:
+        raise ValueError("regularisers need the camera constants")
+    return None, torch.empty(0, device=image.device)
 
 
 class _TrainLoss(torch.autograd.Function):
@@ -203,36 +250,19 @@ class _TrainLoss(torch.autograd.Function):
         out = torch.empty((6,), dtype=torch.float32, device=dev)
         total = torch.empty((), dtype=torch.float32, device=dev)
         s = _n.current_stream_ptr(dev)
-        am = pb = None
-        npost = 0
         with torch.cuda.device(dev):
-            if reg and planes == 3 and FUSED_LOSS:
-                # both halves in one launch (csrc/train_fused.hip): they share no data, their workgroups run side by side
-                am = allmap.detach().contiguous().float()
-                npost = ((W + 15) // 16) * ((H + 15) // 16)
-                pb = torch.empty((npost, 2), dtype=torch.float32, device=dev)
-                _check(lib.surfel_train_loss_forward(H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), _n.ptr(am), _n.ptr(cam),
-                                                     float(depth_ratio), _n.ptr(pb), s), "surfel_train_loss_forward")
-            else:
-                _check(lib.surfel_l1_ssim_forward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), s), "surfel_l1_ssim_forward")
-                if reg:
-                    am = allmap.detach().contiguous().float()
-                    npost = ((W + 15) // 16) * ((H + 15) // 16)
-                    pb = torch.empty((npost, 2), dtype=torch.float32, device=dev)
-                    # maps = NULL: only the two regulariser sums are needed (the backward recomputes from allmap)
-                    _check(lib.surfel_render_post_forward(H, W, _n.ptr(am), _n.ptr(cam), float(depth_ratio), None, _n.ptr(pb), s),
-                           "surfel_render_post_forward")
+            am, pb = _loss_forward(lib, planes, H, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg, s)
             # defer_scalars: the loss scalars are written by an extra workgroup of the fused BACKWARD launch (valid once the backward has
             # run: a training loop reads them after the step) — one launch less per iteration
             ctx.deferred = None
             if defer_scalars and reg and planes == 3 and FUSED_LOSS and (image.requires_grad or getattr(ctx, "manual", False)):
                 ctx.deferred = (partials, pb, out, total)
             else:
-                _check(lib.surfel_loss_finalize(_n.ptr(partials), planes * nblk, planes * H * W, _n.ptr(pb), npost, H * W, float(lambda_dssim),
-                                                float(lambda_normal) if reg else 0.0, float(lambda_dist) if reg else 0.0, _n.ptr(out), _n.ptr(total), s),
-                       "surfel_loss_finalize")
+                _check(lib.surfel_loss_finalize(_n.ptr(partials), planes * nblk, planes * H * W, _n.ptr(pb), 0 if pb is None else pb.shape[0], H * W,
+                                                float(lambda_dssim), float(lambda_normal) if reg else 0.0, float(lambda_dist) if reg else 0.0,
+                                                _n.ptr(out), _n.ptr(total), s), "surfel_loss_finalize")
         ctx.set_materialize_grads(False)
-        ctx.k = (planes, H, W, float(depth_ratio), float(lambda_dssim), float(lambda_normal), float(lambda_dist), reg)
+        ctx.k = (planes, H, W, float(depth_ratio), float(lambda_dssim), float(lambda_normal), float(lambda_dist))
         ctx.shapes = (tuple(image.shape), None if allmap is None else tuple(allmap.shape))
         ctx.save_for_backward(x, y, dmaps, am, cam)
         ctx.mark_non_differentiable(out)
@@ -240,32 +270,18 @@ class _TrainLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, g_out):
-        planes, H, W, ratio, lam, ln, ld, reg = ctx.k
+        planes, H, W, ratio, lam, ln, ld = ctx.k
         x, y, dmaps, am, cam = ctx.saved_tensors
         if g_total is None:
             return None, None, None, None, None, None, None, None, None
         dev = x.device
-        lib = _n.load()
         N = float(planes * H * W)
         g = g_total.contiguous().float().reshape(1)
-        grad_img = torch.empty_like(x)
-        grad_am = None
-        s = _n.current_stream_ptr(dev)
+        d = ctx.deferred or (None, None, None, None)
         with torch.cuda.device(dev):
-            if reg and planes == 3 and FUSED_LOSS:
-                grad_am = torch.empty_like(am)
-                fin = ctx.deferred or (None, None, None, None)
-                _check(lib.surfel_train_loss_backward(H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), (1.0 - lam) / N, -lam / N, _n.ptr(am), _n.ptr(cam),
-                                                      ratio, ln / (H * W), ld / (H * W), _n.ptr(g), _n.ptr(grad_img), _n.ptr(grad_am),
-                                                      _n.ptr(fin[0]), _n.ptr(fin[1]), lam, ln, ld, _n.ptr(fin[2]), _n.ptr(fin[3]), s),
-                       "surfel_train_loss_backward")
-            else:
-                _check(lib.surfel_l1_ssim_backward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), (1.0 - lam) / N, -lam / N, _n.ptr(g), _n.ptr(g),
-                                                   _n.ptr(grad_img), s), "surfel_l1_ssim_backward")
-                if reg:
-                    grad_am = torch.empty_like(am)
-                    _check(lib.surfel_render_post_backward(H, W, _n.ptr(am), _n.ptr(cam), ratio, None, ln / (H * W), ld / (H * W), _n.ptr(g),
-                                                           _n.ptr(grad_am), s), "surfel_render_post_backward")
+            grad_img, grad_am = _loss_backward(_n.load(), planes, H, W, x, y, dmaps, am, cam, ratio,
+                                               ((1.0 - lam) / N, -lam / N, ln / (H * W), ld / (H * W)), g,
+                                               (d[0], d[1], lam, ln, ld, d[2], d[3]), _n.current_stream_ptr(dev))
         return grad_img.view(ctx.shapes[0]), grad_am, None, None, None, None, None, None, None
 
 
@@ -274,22 +290,14 @@ def train_loss(image, allmap, gt_image, cam_consts, depth_ratio, lambda_dssim, l
     (surfel_render.post_consts) or None when both regulariser weights are 0.
     defer_scalars: the returned scalars (and the total's VALUE) are filled in by the backward launch instead of a finalize launch
     of their own — for a training loop that calls backward right away and reads them afterwards; gradients do not depend on it."""
-    if cam_consts is None:
-        if lambda_normal != 0.0 or lambda_dist != 0.0:
-            raise ValueError("regularisers need the camera constants")
-        cam_consts = torch.empty(0, device=image.device)
-        allmap = None
+    allmap, cam_consts = _regulariser_inputs(image, allmap, cam_consts, lambda_normal, lambda_dist)
     return _TrainLoss.apply(image, allmap, gt_image, cam_consts, depth_ratio, lambda_dssim, lambda_normal, lambda_dist, defer_scalars)
 
 
 def train_loss_manual(image, allmap, gt_image, cam_consts, depth_ratio, lambda_dssim, lambda_normal, lambda_dist, defer_scalars=True):
     """train_loss without autograd: returns (ctx, total, scalars); train_loss_manual_backward(ctx, g_total) then yields
     (dL/dimage, dL/dallmap or None).  Same kernels, same bits as the autograd node (call under torch.no_grad())."""
-    if cam_consts is None:
-        if lambda_normal != 0.0 or lambda_dist != 0.0:
-            raise ValueError("regularisers need the camera constants")
-        cam_consts = torch.empty(0, device=image.device)
-        allmap = None
+    allmap, cam_consts = _regulariser_inputs(image, allmap, cam_consts, lambda_normal, lambda_dist)
     ctx = _n.ManualCtx()
     total, out = _TrainLoss.forward(ctx, image, allmap, gt_image, cam_consts, depth_ratio, lambda_dssim, lambda_normal, lambda_dist, defer_scalars)
     return ctx, total, out
@@ -317,7 +325,6 @@ class _TrainLossBand(torch.autograd.Function):
         planes, He, W = _planes(image, gt)
         x = image.detach().contiguous().float(); y = gt.detach().contiguous().float()
         dev = x.device
-        lib = _n.load()
         reg = (lambda_normal != 0.0 or lambda_dist != 0.0) and allmap is not None
         a, b = int(rows[0]), int(rows[1])
         if a % 32 != 0 or (b % 32 != 0 and b != He):
@@ -326,21 +333,8 @@ class _TrainLossBand(torch.autograd.Function):
         nbx, nby = (W + 31) // 32, (He + 31) // 32
         dmaps = torch.empty((3, planes, He, W), dtype=torch.float32, device=dev)
         partials = torch.empty((planes * nbx * nby, 2), dtype=torch.float32, device=dev)
-        s = _n.current_stream_ptr(dev)
-        am = pb = None
         with torch.cuda.device(dev):
-            if reg and planes == 3 and FUSED_LOSS:
-                am = allmap.detach().contiguous().float()
-                pb = torch.empty((((W + 15) // 16) * ((He + 15) // 16), 2), dtype=torch.float32, device=dev)
-                _check(lib.surfel_train_loss_forward(He, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), _n.ptr(am), _n.ptr(cam),
-                                                     float(depth_ratio), _n.ptr(pb), s), "surfel_train_loss_forward")
-            else:
-                _check(lib.surfel_l1_ssim_forward(planes, He, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), s), "surfel_l1_ssim_forward")
-                if reg:
-                    am = allmap.detach().contiguous().float()
-                    pb = torch.empty((((W + 15) // 16) * ((He + 15) // 16), 2), dtype=torch.float32, device=dev)
-                    _check(lib.surfel_render_post_forward(He, W, _n.ptr(am), _n.ptr(cam), float(depth_ratio), None, _n.ptr(pb), s),
-                           "surfel_render_post_forward")
+            am, pb = _loss_forward(_n.load(), planes, He, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg, _n.current_stream_ptr(dev))
         sums = torch.zeros((4,), dtype=torch.float32, device=dev)
         sums[0:2] = partials.view(planes, nby, nbx, 2)[:, a // 32:(b + 31) // 32].sum((0, 1, 2))
         if reg:
@@ -348,7 +342,7 @@ class _TrainLossBand(torch.autograd.Function):
         N3, N1 = float(planes * Hf * Wf), float(Hf * Wf)
         share = ((1.0 - lambda_dssim) * sums[0] - lambda_dssim * sums[1]) / N3 + (lambda_normal * sums[2] + lambda_dist * sums[3]) / N1
         ctx.set_materialize_grads(False)
-        ctx.k = (planes, He, W, float(depth_ratio), float(lambda_dssim), float(lambda_normal), float(lambda_dist), reg, N3, N1)
+        ctx.k = (planes, He, W, float(depth_ratio), float(lambda_dssim), float(lambda_normal), float(lambda_dist), N3, N1)
         ctx.shapes = (tuple(image.shape), None if allmap is None else tuple(allmap.shape))
         ctx.save_for_backward(x, y, dmaps, am, cam)
         ctx.mark_non_differentiable(sums)
@@ -356,30 +350,15 @@ class _TrainLossBand(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_share, g_sums):
-        planes, He, W, ratio, lam, ln, ld, reg, N3, N1 = ctx.k
+        planes, He, W, ratio, lam, ln, ld, N3, N1 = ctx.k
         x, y, dmaps, am, cam = ctx.saved_tensors
         if g_share is None:
             return (None,) * 10
         dev = x.device
-        lib = _n.load()
         g = g_share.contiguous().float().reshape(1)
-        grad_img = torch.empty_like(x)
-        grad_am = None
-        s = _n.current_stream_ptr(dev)
         with torch.cuda.device(dev):
-            if reg and planes == 3 and FUSED_LOSS:
-                grad_am = torch.empty_like(am)
-                _check(lib.surfel_train_loss_backward(He, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), (1.0 - lam) / N3, -lam / N3, _n.ptr(am), _n.ptr(cam),
-                                                      ratio, ln / N1, ld / N1, _n.ptr(g), _n.ptr(grad_img), _n.ptr(grad_am),
-                                                      None, None, 0.0, 0.0, 0.0, None, None, s),
-                       "surfel_train_loss_backward")
-            else:
-                _check(lib.surfel_l1_ssim_backward(planes, He, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), (1.0 - lam) / N3, -lam / N3, _n.ptr(g), _n.ptr(g),
-                                                   _n.ptr(grad_img), s), "surfel_l1_ssim_backward")
-                if reg:
-                    grad_am = torch.empty_like(am)
-                    _check(lib.surfel_render_post_backward(He, W, _n.ptr(am), _n.ptr(cam), ratio, None, ln / N1, ld / N1, _n.ptr(g),
-                                                           _n.ptr(grad_am), s), "surfel_render_post_backward")
+            grad_img, grad_am = _loss_backward(_n.load(), planes, He, W, x, y, dmaps, am, cam, ratio, ((1.0 - lam) / N3, -lam / N3, ln / N1, ld / N1),
+                                               g, (None, None, 0.0, 0.0, 0.0, None, None), _n.current_stream_ptr(dev))
         return (grad_img.view(ctx.shapes[0]), grad_am) + (None,) * 8
 
 
@@ -387,11 +366,7 @@ def train_loss_band(image_ext, allmap_ext, gt_ext, cam_consts_ext, depth_ratio, 
     """Band share of train.py:72-88's loss for tile-band sharding: the shares of all ranks add up to the full-image loss
     (without the constant lambda_dssim term), their gradients are the unsharded ones.  rows = (first, end) band rows inside the
     extended region, full_hw = (H, W) of the whole image, cam_consts_ext = surfel_render.post_consts_rows(...)."""
-    if cam_consts_ext is None:
-        if lambda_normal != 0.0 or lambda_dist != 0.0:
-            raise ValueError("regularisers need the camera constants")
-        cam_consts_ext = torch.empty(0, device=image_ext.device)
-        allmap_ext = None
+    allmap_ext, cam_consts_ext = _regulariser_inputs(image_ext, allmap_ext, cam_consts_ext, lambda_normal, lambda_dist)
     return _TrainLossBand.apply(image_ext, allmap_ext, gt_ext, cam_consts_ext, depth_ratio, lambda_dssim, lambda_normal, lambda_dist, rows, full_hw)
 
 

@@ -13,7 +13,6 @@ re-create the parameters (densification), Adam(eps=1e-15).  Multi-GPU: G views p
 densification statistics are accumulated locally and all-reduced only when a densification is due.
 """
 import math
-import os
 import random
 import time
 from types import SimpleNamespace
@@ -169,10 +168,11 @@ class Trainer:
         self.last = {}
         self._epoch, self._epoch_views, self._epoch_campos, self._centers = -1, None, None, None
         self._one = torch.ones((), dtype=torch.float32, device=model.device)
-        self.defer_scalars = os.environ.get("SURFEL_DEFER_SCALARS", "1") != "0"      # loss scalars by the fused loss backward launch instead of a finalize launch
-        self.lazy_count = os.environ.get("SURFEL_LAZY_COUNT", "1") != "0"      # forward without the host wait for the instance count (step())
+        # test handles (tests/test_gpu_train.py compares each with its bit-identical alternative)
+        self.lazy_count = True          # forward without the host wait for the instance count (_forward_backward)
         self.lazy_overflows = 0
-        self.manual_chain = os.environ.get("SURFEL_MANUAL_CHAIN", "1") != "0"      # forward / backward of the iteration driven without autograd (step())
+        self.manual_chain = True        # forward / backward of the iteration driven without autograd (_forward_backward)
+        self.fused_update = True        # statistics + Adam in one launch (surfel_train_update) where nothing comes between them
         self.views_per_step = 1         # single process: > 1 = accumulate that many views per optimiser step (_step_accumulate)
         self.rebalance_every = 8        # bands: iterations between re-balancing the band edges (one small all-gather + D2H)
         self._row_weights = None        # bands: running mean of tile instances per 16-row tile row (host list) of frames of ...
@@ -195,10 +195,6 @@ class Trainer:
         self.early_gather_probe = None      # {"early_ms": .., "late_ms": .., "choice": ..} once decided
         self._eg_events, self._eg_first, self._eg_failed = [], None, False
         self._early, self._early_err = None, None
-        # fused SH path (default): the rasterizer's backward skips the 192 B/surfel SH gradients, the optimiser kernel rebuilds them
-        # from the 12 B/surfel colour gradients.  Always on under view-parallel training (that is how the gradients are exchanged).
-        self.fused_sh = self._exchange or os.environ.get("SURFEL_SH_FUSED", "1") != "0"
-        self.fused_update = os.environ.get("SURFEL_FUSED_UPDATE", "1") != "0"      # surfel_train_update (statistics + Adam in one launch)
         if model.grad is None:
             model.training_setup(self.opt)
         if self.world > 1:
@@ -252,74 +248,85 @@ class Trainer:
         """One training iteration (train.py:54-138).  Returns nothing; `self.last` holds device scalars for logging."""
         if self.world == 1 and self.views_per_step > 1:
             return self._step_accumulate(self.views_per_step)
-        self.iteration += 1
-        it, opt, m = self.iteration, self.opt, self.model
-        m.update_learning_rate(it)
-        if it % getattr(opt, "sh_degree_interval", 1000) == 0:
-            m.oneupSHdegree()
+        it, lam_n, lam_d = self._begin_step()
         cam = self._next_camera()
-        m.bind(sh_grad=not self.fused_sh)      # fused: the SH gradients are rebuilt inside the optimiser kernel from the colour gradients
-        bands = self.world > 1 and self.sharding == "bands"
-        lam_n = opt.lambda_normal if it > opt.normal_from_iter else 0.0
-        lam_d = opt.lambda_dist if it > opt.dist_from_iter else 0.0
-        reg = lam_n > 0.0 or lam_d > 0.0
-        stats_live = it < opt.densify_until_iter
-        if bands:
-            H, W = int(cam.image_height), int(cam.image_width)
-            if self._row_weights_hw != (H, W):      # real capture sets mix resolutions: the running weights belong to one of them
-                self._row_weights, self._row_weights_hw = None, (H, W)
-            bounds = surfel_dist.band_bounds(H, self.world, self._row_weights, multiple=surfel_dist.HALO)
-            y0, y1 = bounds[self.rank]
-            # the densification statistic of the view = norm of the SUM over bands: it rides in the same all-reduce, right
-            # behind the colour block (both live in the SH section of the gradient store, unused in fused-SH mode)
-            arena2d = m.grad[(GEOM_FLOATS + COLOUR_FLOATS) * m.P:(GEOM_FLOATS + COLOUR_FLOATS + 3) * m.P].view(m.P, 3)
-            import diff_surfel_rasterization as dsr
-            dsr._grad_arena["means2D"] = arena2d
-            image_b, radii, allmap_b, means2D = rasterize(cam, m, self.pipe, self.background, zero_means2D=False, band=(y0, y1))
-            ext = surfel_dist.exchange_halo(torch.cat([image_b, allmap_b], 0) if reg else image_b, bounds, H)
-            top, bot = surfel_dist.halo_rows(bounds, self.rank, H)
-            gt_ext = cam.original_image[:, y0 - top:y1 + bot]
-            consts = post_consts_rows(cam.post_consts(), y0 - top) if reg else None
-            loss, sums = train_loss_band(ext[:3], ext[3:] if reg else None, gt_ext, consts, self.pipe.depth_ratio, opt.lambda_dssim, lam_n, lam_d,
-                                         (top, top + (y1 - y0)), (H, W))
-            sums = sums.clone()
-            dist.all_reduce(sums, op=dist.ReduceOp.SUM)           # 16 bytes: the full-image loss terms, for logging
-            scalars = scalars_from_band_sums(sums, float(3 * H * W), float(H * W), opt.lambda_dssim, lam_n, lam_d)
-            halo_b = surfel_dist.halo_bytes(bounds, self.rank, H, W, 10 if reg else 3)
+        self.model.bind(sh_grad=False)      # the SH gradients are rebuilt inside the optimiser kernel from the colour gradients
+        if self.world > 1 and self.sharding == "bands":
+            self._step_band(it, cam, lam_n, lam_d)
         else:
-            halo_b = 0
-        self.wire = surfel_dist.wire_bytes_per_step(m.P, self.world, self.sharding, stats_live, halo_b)
-        early = (not bands) and self._probe_early_gather() and self._async_exchange and it < opt.iterations
-        # Lazily counted forward (include/surfel_hip.h: SURFEL_OPT_LAZY_COUNT): the host does not wait for the frame's instance count in
-        # the middle of the iteration — it enqueues loss and backward behind the forward and collects the count afterwards, when it has
-        # long arrived; a frame that overflowed its binning capacity (rare) is rendered again with exact sizes, loss and backward with
-        # it, before anything irreversible (statistics, optimiser step, collectives) has happened.
-        lazy = self.lazy_count and not bands and not early
-        # The iteration's chain is fixed (rasterizer -> loss -> loss backward -> rasterizer backward): driven by hand
-        # (surfel_native.ManualCtx) it costs a fraction of the host time autograd spends on it — engine, worker-thread hand-over, five
-        # parameter gates — with the same kernels and bits; compute_cov3D_python trains through PyTorch code and needs autograd.
-        manual = self.manual_chain and not bands and not getattr(self.pipe, "compute_cov3D_python", False)
-        g2d = None
+            self._step_view(it, cam, lam_n, lam_d)
+
+    def _begin_step(self):
+        """Advance the iteration, set its learning rate and SH degree; returns (iteration, lambda_normal, lambda_dist)."""
+        self.iteration += 1
+        it, opt = self.iteration, self.opt
+        self.model.update_learning_rate(it)
+        if it % getattr(opt, "sh_degree_interval", 1000) == 0:
+            self.model.oneupSHdegree()
+        return it, (opt.lambda_normal if it > opt.normal_from_iter else 0.0), (opt.lambda_dist if it > opt.dist_from_iter else 0.0)
+
+    def _step_view(self, it, cam, lam_n, lam_d):
+        """One GPU, or view-parallel (N ranks, or the world-1 rehearsal): every rank trains on its own view."""
+        opt, m = self.opt, self.model
+        stats_live = it < opt.densify_until_iter
+        self.wire = surfel_dist.wire_bytes_per_step(m.P, self.world, self.sharding, stats_live)
+        early = self._probe_early_gather() and self._async_exchange and it < opt.iterations
+        radii, scalars, g2d = self._forward_backward(cam, lam_n, lam_d, early)
+        self.last = dict(loss=scalars[5], scalars=scalars, points=m.P, radii=radii)     # [Ll1, ssim, normal_err, dist, photometric, total] on the device
+        with torch.no_grad():
+            if self.fused_update and not self._exchange and it < opt.iterations and not self._is_event_iteration(it):
+                # statistics + optimiser step as ONE launch where nothing can come between them (single GPU, no densification /
+                # opacity reset this iteration): two launch boundaries and the statistics' latency-bound kernel fewer
+                m.update_step((cam.camera_center[None], m.gcol[None]), stats=(g2d, radii) if stats_live else None)
+                return
+            rebuilt = False
+            if stats_live:
+                m.add_densification_stats(g2d, radii=radii)
+                rebuilt = self._schedule_events(it)
+            if it < opt.iterations and not rebuilt:     # re-created parameters carry no gradient in the reference: no update
+                if self._exchange:
+                    self._exchange_step()
+                else:
+                    m.optimizer_step(grad_scale=1.0, colour_grads=(cam.camera_center[None], m.gcol[None]))
+            if self._early is not None:      # an iteration without an optimiser step (parameters re-created): retire the gather
+                self._early[1].wait()
+                self._early = None
+
+    def _forward_backward(self, cam, lam_n, lam_d, early):
+        """Render, loss and backward of one view; returns (radii, loss scalars, dL/dmeans2D).
+        Lazily counted forward (include/surfel_hip.h: SURFEL_OPT_LAZY_COUNT): the host does not wait for the frame's instance count in
+        the middle of the iteration — it enqueues loss and backward behind the forward and collects the count afterwards, when it has
+        long arrived; a frame that overflowed its binning capacity (rare) is rendered again with exact sizes, loss and backward with
+        it, before anything irreversible (statistics, optimiser step, collectives) has happened.
+        The chain (rasterizer -> loss -> loss backward -> rasterizer backward) is fixed: driven by hand (surfel_native.ManualCtx) it
+        costs a fraction of the host time autograd spends on it — engine, worker-thread hand-over, five parameter gates — with the same
+        kernels and bits; compute_cov3D_python trains through PyTorch code and needs autograd.
+        early: the colour all-gather starts inside the rasterizer's backward (_on_colour_ready)."""
+        opt, m, pipe = self.opt, self.model, self.pipe
+        reg = lam_n > 0.0 or lam_d > 0.0
+        lazy = self.lazy_count and not early
+        manual = self.manual_chain and not getattr(pipe, "compute_cov3D_python", False)
         for bits in ((_n.OPT_LAZY_COUNT, _n.OPT_EXACT_BINNING) if lazy else (0,)):
+            loss_args = (pipe.depth_ratio, opt.lambda_dssim, lam_n, lam_d)
             if manual:
                 with torch.no_grad():
-                    rctx, image, radii, allmap = rasterize_manual(cam, m, self.pipe, self.background, debug_bits=bits)
+                    rctx, image, radii, allmap = rasterize_manual(cam, m, pipe, self.background, debug_bits=bits)
                     lctx, loss, scalars = train_loss_manual(image, allmap if reg else None, cam.original_image, cam.post_consts() if reg else None,
-                                                            self.pipe.depth_ratio, opt.lambda_dssim, lam_n, lam_d, defer_scalars=self.defer_scalars)
-            elif not bands:
-                image, radii, allmap, means2D = rasterize(cam, m, self.pipe, self.background, zero_means2D=False, debug_bits=bits)
+                                                            *loss_args, defer_scalars=True)
+            else:
+                image, radii, allmap, means2D = rasterize(cam, m, pipe, self.background, zero_means2D=False, debug_bits=bits)
                 loss, scalars = train_loss(image, allmap if reg else None, cam.original_image, cam.post_consts() if reg else None,
-                                           self.pipe.depth_ratio, opt.lambda_dssim, lam_n, lam_d, defer_scalars=self.defer_scalars)      # (read after the backward below)
+                                           *loss_args, defer_scalars=True)      # (read after the backward below)
             if early:
                 self._early, self._early_err = None, None
                 _n.set_backward_hook(self._on_colour_ready)
             try:
                 if manual:
                     with torch.no_grad():
-                        g_img, g_am = train_loss_manual_backward(lctx, self._one)
-                        g2d = rasterize_manual_backward(rctx, g_img, g_am)
+                        g2d = rasterize_manual_backward(rctx, *train_loss_manual_backward(lctx, self._one))
                 else:
                     torch.autograd.backward(loss, grad_tensors=self._one)        # cached seed gradient: no ones_like fill per iteration
+                    g2d = means2D.grad
             finally:
                 if early:
                     _n.set_backward_hook(None)
@@ -344,58 +351,74 @@ class Trainer:
             else:
                 self.early_gather = False
             self._early, self._early_err = None, None
-        self.last = dict(loss=scalars[5], scalars=scalars, points=m.P, radii=radii)     # [Ll1, ssim, normal_err, dist, photometric, total] on the device
+        return radii, scalars, g2d
+
+    def _exchange_step(self):
+        """View-parallel optimiser step: all-reduce of the 40 B/surfel geometry prefix + all-gather of 12 B/surfel/rank colour
+        gradients; the 192 B/surfel SH gradients are rebuilt from them (exact, rank-ordered sum) instead of being all-reduced."""
+        m = self.model
+        campos_all = self._step_views()[1]
+        scale = 1.0 / self.world      # views: average
+        if not self._async_exchange:
+            gcol_all = exchange_collectives(m.grad, m.gcol, m.P)
+            m.optimizer_step(grad_scale=scale, colour_grads=(campos_all, gcol_all))
+            return
+        if self._early is not None:      # the gather has been in flight since the middle of the backward
+            gcol_all, w_gather = self._early
+            self._early = None
+            w_reduce = dist.all_reduce(m.grad[:GEOM_FLOATS * m.P], op=dist.ReduceOp.SUM, async_op=True)
+        else:
+            gcol_all, w_gather, w_reduce = exchange_collectives(m.grad, m.gcol, m.P, async_op=True)
+        self._timed_wait(w_gather)   # stream-level wait: the SH block updates while the geometry all-reduce is in flight
+        m.optimizer_step(grad_scale=scale, colour_grads=(campos_all, gcol_all), parts=1)
+        self._timed_wait(w_reduce)
+        m.optimizer_step(grad_scale=scale, colour_grads=(campos_all, gcol_all), parts=2)
+
+    def _step_band(self, it, cam, lam_n, lam_d):
+        """Tile-band sharding (N > 1): every rank renders its row band of the SAME view (see __init__)."""
+        opt, m = self.opt, self.model
+        reg = lam_n > 0.0 or lam_d > 0.0
+        stats_live = it < opt.densify_until_iter
+        H, W = int(cam.image_height), int(cam.image_width)
+        if self._row_weights_hw != (H, W):      # real capture sets mix resolutions: the running weights belong to one of them
+            self._row_weights, self._row_weights_hw = None, (H, W)
+        bounds = surfel_dist.band_bounds(H, self.world, self._row_weights, multiple=surfel_dist.HALO)
+        y0, y1 = bounds[self.rank]
+        # the densification statistic of the view = norm of the SUM over bands: it rides in the same all-reduce, right
+        # behind the colour block (both live in the SH section of the gradient store, unused in fused-SH mode)
+        arena2d = m.grad[(GEOM_FLOATS + COLOUR_FLOATS) * m.P:(GEOM_FLOATS + COLOUR_FLOATS + 3) * m.P].view(m.P, 3)
+        import diff_surfel_rasterization as dsr
+        dsr._grad_arena["means2D"] = arena2d
+        image_b, radii, allmap_b, _ = rasterize(cam, m, self.pipe, self.background, zero_means2D=False, band=(y0, y1))
+        ext = surfel_dist.exchange_halo(torch.cat([image_b, allmap_b], 0) if reg else image_b, bounds, H)
+        top, bot = surfel_dist.halo_rows(bounds, self.rank, H)
+        gt_ext = cam.original_image[:, y0 - top:y1 + bot]
+        consts = post_consts_rows(cam.post_consts(), y0 - top) if reg else None
+        loss, sums = train_loss_band(ext[:3], ext[3:] if reg else None, gt_ext, consts, self.pipe.depth_ratio, opt.lambda_dssim, lam_n, lam_d,
+                                     (top, top + (y1 - y0)), (H, W))
+        sums = sums.clone()
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM)           # 16 bytes: the full-image loss terms, for logging
+        scalars = scalars_from_band_sums(sums, float(3 * H * W), float(H * W), opt.lambda_dssim, lam_n, lam_d)
+        self.wire = surfel_dist.wire_bytes_per_step(m.P, self.world, self.sharding, stats_live,
+                                                    surfel_dist.halo_bytes(bounds, self.rank, H, W, 10 if reg else 3))
+        torch.autograd.backward(loss, grad_tensors=self._one)
+        self.last = dict(loss=scalars[5], scalars=scalars, points=m.P, radii=radii)
         with torch.no_grad():
+            # ONE all-reduce: geometry 10 | colour 3 (| means2D statistic 3) floats per surfel
+            n_f = GEOM_FLOATS + COLOUR_FLOATS + (3 if stats_live else 0)
+            w_same = dist.all_reduce(m.grad[:n_f * m.P], op=dist.ReduceOp.SUM, async_op=self._async_exchange)
+            if stats_live:
+                radii = radii.clone(); dist.all_reduce(radii, op=dist.ReduceOp.MAX)      # visibility = union of the bands
+            if self._async_exchange:
+                self._timed_wait(w_same)
+            self._rebalance_bands(cam)
             rebuilt = False
-            w_same = None
-            if bands:
-                # ONE all-reduce: geometry 10 | colour 3 (| means2D statistic 3) floats per surfel
-                n_f = GEOM_FLOATS + COLOUR_FLOATS + (3 if stats_live else 0)
-                w_same = dist.all_reduce(m.grad[:n_f * m.P], op=dist.ReduceOp.SUM, async_op=self._async_exchange)
-                if stats_live:
-                    radii = radii.clone(); dist.all_reduce(radii, op=dist.ReduceOp.MAX)      # visibility = union of the bands
-                if self._async_exchange:
-                    self._timed_wait(w_same)
-                self._rebalance_bands(cam)
-            # statistics + optimiser step as ONE launch where nothing can come between them (single GPU, SH block rebuilt in the kernel,
-            # no densification / opacity reset this iteration): two launch boundaries and the statistics' latency-bound kernel fewer
-            one_launch = self.fused_update and self.fused_sh and not bands and not self._exchange and it < opt.iterations and not self._is_event_iteration(it)
-            if one_launch:
-                m.update_step((cam.camera_center[None], m.gcol[None]), stats=((g2d if manual else means2D.grad), radii) if stats_live else None)
-                rebuilt = True      # (nothing left to do below)
-            elif stats_live:
-                m.add_densification_stats(arena2d if bands else (g2d if manual else means2D.grad), radii=radii)
-                rebuilt = self._schedule_events(it, bands)
-            if it < opt.iterations and not rebuilt:     # re-created parameters carry no gradient in the reference: no update
-                if bands:
-                    # partial gradients of one view add up (no averaging); the SH block is rebuilt from the summed colour gradients
-                    m.optimizer_step(grad_scale=1.0, colour_grads=(cam.camera_center[None], m.gcol[None]))
-                elif self._exchange:
-                    # all-reduce of the 40 B/surfel geometry prefix + all-gather of 12 B/surfel/rank colour gradients; the 192 B/surfel
-                    # SH gradients are rebuilt from them (exact, rank-ordered sum) instead of being all-reduced
-                    campos_all = self._step_views()[1]
-                    scale = 1.0 / self.world      # views: average
-                    if self._async_exchange:
-                        if self._early is not None:      # the gather has been in flight since the middle of the backward
-                            gcol_all, w_gather = self._early
-                            self._early = None
-                            w_reduce = dist.all_reduce(m.grad[:GEOM_FLOATS * m.P], op=dist.ReduceOp.SUM, async_op=True)
-                        else:
-                            gcol_all, w_gather, w_reduce = exchange_collectives(m.grad, m.gcol, m.P, async_op=True)
-                        self._timed_wait(w_gather)   # stream-level wait: the SH block updates while the geometry all-reduce is in flight
-                        m.optimizer_step(grad_scale=scale, colour_grads=(campos_all, gcol_all), parts=1)
-                        self._timed_wait(w_reduce)
-                        m.optimizer_step(grad_scale=scale, colour_grads=(campos_all, gcol_all), parts=2)
-                    else:
-                        gcol_all = exchange_collectives(m.grad, m.gcol, m.P)
-                        m.optimizer_step(grad_scale=scale, colour_grads=(campos_all, gcol_all))
-                else:
-                    if self.fused_sh:
-                        campos_all, gcol_all = cam.camera_center[None], m.gcol[None]
-                    m.optimizer_step(grad_scale=1.0, colour_grads=(campos_all, gcol_all) if self.fused_sh else None)
-            if self._early is not None:      # an iteration without an optimiser step (parameters re-created): retire the gather
-                self._early[1].wait()
-                self._early = None
+            if stats_live:
+                m.add_densification_stats(arena2d, radii=radii)
+                rebuilt = self._schedule_events(it, bands=True)
+            if it < opt.iterations and not rebuilt:
+                # partial gradients of one view add up (no averaging); the SH block is rebuilt from the summed colour gradients
+                m.optimizer_step(grad_scale=1.0, colour_grads=(cam.camera_center[None], m.gcol[None]))
 
     EG_WARM, EG_LEN = 2, 4      # start-up probe: iterations skipped, iterations per setting
 
@@ -483,18 +506,13 @@ class Trainer:
         """One optimiser step on the AVERAGED gradients of n views rendered one after the other on this GPU — the optimisation
         semantics of n view-parallel ranks (same view schedule: surfel_dist.epoch_schedule; per-view densification statistics;
         SH gradients rebuilt from the n views' colour gradients) without the processes.  Used by the PSNR-parity experiment."""
-        self.iteration += 1
-        it, opt, m = self.iteration, self.opt, self.model
-        m.update_learning_rate(it)
-        if it % getattr(opt, "sh_degree_interval", 1000) == 0:
-            m.oneupSHdegree()
+        it, lam_n, lam_d = self._begin_step()
+        opt, m = self.opt, self.model
         per_epoch = max(1, len(self.cams) // n)
         epoch, k = divmod(it - 1, per_epoch)
         if self._epoch != epoch:
             self._epoch, self._epoch_views = epoch, surfel_dist.epoch_schedule(len(self.cams), n, epoch, self.seed)
         views = [self.cams[v] for v in self._epoch_views[k]]
-        lam_n = opt.lambda_normal if it > opt.normal_from_iter else 0.0
-        lam_d = opt.lambda_dist if it > opt.dist_from_iter else 0.0
         reg = lam_n > 0.0 or lam_d > 0.0
         geo = torch.zeros(GEOM_FLOATS * m.P, device=m.device)
         gcols = torch.empty((n, m.P, 3), device=m.device)

@@ -290,6 +290,172 @@ def test_lazy_redo_on_one_rank_keeps_the_collectives_in_step():
     assert all(a != b for a, b in zip(views0, views1))             # distinct views per iteration across the ranks
 
 
+def _band_step_worker(rank, world, port, q):
+    """Whole Trainer.step()s with sharding="bands" over gloo: rasterizer, band loss and tile-row counts faked; the halo exchange and
+    the collectives are the real ones.  Every all-reduce, statistics update and optimiser step is logged per iteration."""
+    import os
+    import sys
+    import types
+    import torch
+    import torch.distributed as dist
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(here, "2d-gaussian-splatting_amd"))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import diff_surfel_rasterization as dsr
+        import surfel_trainer as TR
+        P, H, W = 7, 128, 8
+        log, bands = [], []
+        base = torch.arange(P * 58, dtype=torch.float32)
+        real_all_reduce = dist.all_reduce
+
+        def logged_all_reduce(t, op=dist.ReduceOp.SUM, group=None, async_op=False):
+            log.append(("all_reduce", t.numel(), str(t.dtype), str(op), t.data_ptr() == model.grad.data_ptr()))
+            return real_all_reduce(t, op=op, group=group, async_op=async_op)
+
+        class FakeModel:
+            device = torch.device("cpu")
+            step_count = 0
+            active_sh_degree = 0
+            theta = m = v = None
+
+            def __init__(self):
+                self.P = P
+                self.grad = base * (rank + 1)
+                self.gcol = self.grad[10 * P:13 * P].view(P, 3)
+                self._gv = {"opacity": torch.ones(P, 1)}
+                self.xyz_gradient_accum, self.denom, self.max_radii2D = torch.zeros(P, 1), torch.zeros(P, 1), torch.zeros(P)
+
+            def update_learning_rate(self, it): pass
+            def oneupSHdegree(self): pass
+            def refresh_activations(self): pass
+            def training_setup(self, opt): pass
+            def reset_opacity(self): log.append(("reset",))
+            def densify_and_prune(self, *a, **k): log.append(("densify",))
+
+            def bind(self, sh_grad=True):
+                log.append(("bind", sh_grad))
+                dsr.set_grad_arena({})
+
+            def add_densification_stats(self, g, radii=None):
+                arena = g.data_ptr() == self.grad[13 * P:].data_ptr() and tuple(g.shape) == (P, 3)
+                log.append(("stats", arena, radii.tolist()))
+
+            def optimizer_step(self, grad_scale=1.0, colour_grads=None, parts=3):
+                campos, gcol = colour_grads
+                log.append(("adam", grad_scale, parts, campos.tolist(), tuple(gcol.shape), gcol.data_ptr() == self.gcol.data_ptr()))
+
+        def fake_rasterize(cam, m, pipe, bg, zero_means2D=True, band=None, debug_bits=0):
+            y0, y1 = band
+            bands.append((y0, y1))
+            log.append(("raster", cam.uid, tuple(band), debug_bits))
+            m.grad.copy_(base * (rank + 1))        # the backward's partial gradients of this rank's band
+            radii = torch.tensor([rank, 1 - rank, 2, 0, 3 * rank, 1, 0], dtype=torch.int32)
+            return (torch.zeros(3, y1 - y0, W, requires_grad=True), radii, torch.zeros(7, y1 - y0, W, requires_grad=True),
+                    torch.zeros(P, 3, requires_grad=True))
+
+        def fake_loss_band(image, allmap, gt, consts, ratio, l_dssim, l_n, l_d, rows, full_hw):
+            log.append(("loss", tuple(image.shape), allmap is not None, tuple(gt.shape), consts is not None, l_n, l_d, tuple(rows), tuple(full_hw)))
+            loss = image.sum() * 0.0 + (allmap.sum() * 0.0 if allmap is not None else 0.0)
+            return loss, torch.tensor([1.0, 2.0, 3.0, 4.0]) * (rank + 1)
+
+        def fake_tile_rows():
+            y0, y1 = bands[-1]
+            return torch.arange(y0 // 16, (y1 + 15) // 16, dtype=torch.int64) + len(bands)
+
+        TR.rasterize = fake_rasterize
+        TR.train_loss_band = fake_loss_band
+        dsr.tile_row_instances = fake_tile_rows
+        cams = [types.SimpleNamespace(uid=i, image_height=H, image_width=W, original_image=torch.zeros(3, H, W),
+                                      camera_center=torch.full((3,), float(i)), post_consts=lambda: torch.zeros(24)) for i in range(3)]
+        opt = TR.optimization_params(iterations=12, densify_from_iter=2, densification_interval=4, densify_until_iter=10, opacity_reset_interval=6,
+                                     dist_from_iter=3, lambda_dist=1.0, normal_from_iter=10 ** 6)
+        model = FakeModel()
+        tr = TR.Trainer(model, cams, opt, TR.pipeline_params(depth_ratio=1.0), extent=1.0, sharding="bands")
+        tr.rebalance_every = 3
+        probes = []
+        tr._probe_early_gather = lambda: probes.append(tr.iteration) or False
+        dist.all_reduce = logged_all_reduce
+        per_it = []
+        for _ in range(opt.iterations):
+            n0 = len(log)
+            tr.step()
+            per_it.append((tr.iteration, log[n0:], dict(tr.wire), float(model.grad[:16 * P].sum()), float(model.grad[16 * P:].sum()),
+                           None if tr._row_weights is None else list(tr._row_weights)))
+        dist.all_reduce = real_all_reduce
+        q.put((rank, per_it, probes))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_band_sharded_step_world2():
+    """Tile-band sharding (Trainer(sharding="bands")): both ranks render a row band of the SAME view, exchange halo rows, evaluate the
+    band loss and back-propagate; then ONE all-reduce of the gradient prefix (geometry + colour, + the means2D statistic while it is
+    live), a MAX all-reduce of the radii while the statistics are live, the band re-balance every `rebalance_every` iterations, the
+    statistics from the means2D arena and one optimiser step on one view's colour gradients — none where the parameters were
+    re-created (two gloo processes, device pieces faked)."""
+    import surfel_dist as sd
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_band_step_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=180) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    P, H, W = 7, 128, 8
+    SUM, MAX = str(dist.ReduceOp.SUM), str(dist.ReduceOp.MAX)
+    total = float(sum(range(P * 58)))
+    views = []
+    for rank, per_it, probes in res:
+        assert probes == []                                                     # no early-gather probe under bands
+        weights, mine = None, []
+        for it, log, wire, prefix, rest, row_weights in per_it:
+            stats_live, reg = it < 10, it > 3
+            densified = stats_live and it > 2 and it % 4 == 0
+            reset = stats_live and it % 6 == 0
+            kinds = [e[0] for e in log]
+            assert log[0] == ("bind", False)                                   # colour gradients: the SH block is rebuilt by the optimiser
+            bounds = sd.band_bounds(H, 2, weights, multiple=sd.HALO)
+            y0, y1 = bounds[rank]
+            top, bot = sd.halo_rows(bounds, rank, H)
+            raster = [e for e in log if e[0] == "raster"]
+            assert len(raster) == 1 and raster[0][2] == (y0, y1) and raster[0][3] == 0
+            mine.append(raster[0][1])
+            He = top + y1 - y0 + bot
+            assert [e for e in log if e[0] == "loss"] == [("loss", (3, He, W), reg, (3, He, W), reg, 0.0, 1.0 if reg else 0.0,
+                                                           (top, top + y1 - y0), (H, W))]
+            n_f = 10 + 3 + (3 if stats_live else 0)
+            expect = [("all_reduce", 4, "torch.float32", SUM, False),          # the band loss sums, for logging
+                      ("all_reduce", n_f * P, "torch.float32", SUM, True)]     # ONE all-reduce of the gradient prefix
+            if stats_live:
+                expect.append(("all_reduce", P, "torch.int32", MAX, False))    # visibility = union of the bands
+            if it % 3 == 0:
+                expect.append(("all_reduce", (H + 15) // 16, "torch.int64", SUM, False))      # re-balance
+            assert [e for e in log if e[0] == "all_reduce"] == expect, (it, log)
+            done = float(sum(range(n_f * P)))
+            assert prefix + rest == 3.0 * done + (rank + 1) * (total - done)    # only the prefix is summed over the ranks
+            assert [e for e in log if e[0] == "stats"] == ([("stats", True, [1, 1, 2, 0, 3, 1, 0])] if stats_live else [])
+            assert kinds.count("densify") == int(densified) and kinds.count("reset") == int(reset)
+            adams = [e for e in log if e[0] == "adam"]
+            if it < 12 and not densified:                                        # opacity-reset-only iterations still step
+                assert adams == [("adam", 1.0, 3, [[float(raster[0][1])] * 3], (1, P, 3), True)]
+                assert kinds.index("adam") > max(i for i, k in enumerate(kinds) if k == "all_reduce")
+            else:
+                assert adams == []
+            assert wire == sd.wire_bytes_per_step(P, 2, "bands", stats_live, sd.halo_bytes(bounds, rank, H, W, 10 if reg else 3))
+            if it % 3 == 0:
+                assert row_weights is not None and row_weights != weights
+                weights = row_weights
+            else:
+                assert row_weights == weights
+        views.append(mine)
+    assert views[0] == views[1]                                                  # both ranks render the same view
+
+
 def _gather_bands_worker(rank, world, port, q):
     import os
     import torch

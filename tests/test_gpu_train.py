@@ -959,7 +959,9 @@ def test_view_parallel_step_rehearsed_on_rccl_with_early_gather():
     take exactly the steps of the gather-after-backward form.  (Halo p2p and > 1 rank: gloo tests in tests/test_dist_cpu.py.)"""
     import torch
     import torch.distributed as dist
+    import diff_surfel_rasterization as dsr
     import surfel_trainer as TR
+    from surfel_model import GEOM_FLOATS
     d = dev()
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29541")
     assert not dist.is_initialized()
@@ -974,7 +976,7 @@ def test_view_parallel_step_rehearsed_on_rccl_with_early_gather():
             m.spatial_lr_scale = 1.0
             tr = TR.Trainer(m, cams, TR.optimization_params(dist_from_iter=0, normal_from_iter=0, lambda_dist=10.0, densify_from_iter=10 ** 9),
                             TR.pipeline_params(depth_ratio=1.0), rehearse_exchange=True)
-            assert tr._exchange and tr._async_exchange and tr.fused_sh
+            assert tr._exchange and tr._async_exchange
             tr.early_gather = early
             calls = []
             if early:
@@ -982,6 +984,10 @@ def test_view_parallel_step_rehearsed_on_rccl_with_early_gather():
                 tr._on_colour_ready = lambda: (calls.append(1), inner())[1]
             for _ in range(4):
                 tr.step()
+            # SH gradients rebuilt from gathered colour gradients: the backward skipped the SH block and wrote dL/dcolour into the
+            # colour block behind the geometry prefix of the gradient store (what the exchange gathers)
+            assert dsr._grad_arena["sh"] is None and dsr._grad_arena["colors"] is m.gcol
+            assert m.gcol.data_ptr() == m.grad[GEOM_FLOATS * m.P:].data_ptr() and tuple(m.gcol.shape) == (m.P, 3)
             torch.cuda.synchronize()
             assert torch.isfinite(tr.last["scalars"]).all() and torch.isfinite(m.theta).all()
             assert len(calls) == (4 if early else 0) and tr._early is None
