@@ -30,6 +30,9 @@ MESH_EXPORTS = ["surfel_tsdf_table_bytes", "surfel_tsdf_block_bytes", "surfel_me
 # include/surfel_mesh_unbounded.h
 UNBOUNDED_EXPORTS = ["surfel_unbounded_bytes", "surfel_unbounded_init", "surfel_unbounded_fuse", "surfel_unbounded_count", "surfel_unbounded_extract",
                      "surfel_unbounded_color"]
+# include/surfel_eval.h
+EVAL_EXPORTS = ["surfel_eval_sample_count", "surfel_eval_sample_emit", "surfel_eval_grid_build", "surfel_eval_thin", "surfel_eval_obs_mask",
+                "surfel_eval_above_plane", "surfel_eval_nearest", "surfel_eval_mean_below", "surfel_eval_dilate_masks", "surfel_eval_cull_vertices"]
 
 # per-call option overrides carried in the upper bits of the `debug` argument (include/surfel_hip.h)
 OPT_NO_CULL = 1 << 8
@@ -75,6 +78,12 @@ class UnboundedVolume(C.Structure):
 class UnboundedView(C.Structure):
     """surfel_unbounded_view of include/surfel_mesh_unbounded.h (64 B; an array of them is copied to the device)"""
     _fields_ = [("proj", C.c_float * 12), ("H", C.c_int32), ("W", C.c_int32), ("offset", C.c_int64)]
+
+
+class EvalGrid(C.Structure):
+    """surfel_eval_grid of include/surfel_eval.h"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int * 3), ("budget_bytes", C.c_int64), ("n", C.c_int64),
+                ("sorted", C.c_void_p), ("order", C.c_void_p), ("ranges", C.c_void_p)]
 
 
 _lib = None
@@ -171,6 +180,21 @@ def load():
                                 ("surfel_unbounded_count", i, [uvol, vp]),
                                 ("surfel_unbounded_extract", i, [uvol, vp, vp, vp]),
                                 ("surfel_unbounded_color", i, [i64, vp, i, vp, vp, vp, f, vp, vp])):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        # ---- include/surfel_eval.h
+        eg, d = C.POINTER(EvalGrid), C.c_double
+        for name, res, args in (("surfel_eval_sample_count", i64, [ALLOC_FN, vp, i64, i64, vp, vp, d, i64, vp, vp]),
+                                ("surfel_eval_sample_emit", i, [i64, i64, vp, vp, d, vp, i64, vp, vp]),
+                                ("surfel_eval_grid_build", i, [ALLOC_FN, vp, eg, i64, vp, vp, vp]),
+                                ("surfel_eval_thin", i, [ALLOC_FN, vp, eg, f, vp, C.POINTER(i), vp]),
+                                ("surfel_eval_obs_mask", i, [i64, vp, C.POINTER(f), f, d, vp, C.POINTER(i), vp, vp, vp]),
+                                ("surfel_eval_above_plane", i, [i64, vp, C.POINTER(d), vp, vp]),
+                                ("surfel_eval_nearest", i, [ALLOC_FN, vp, eg, i64, vp, f, vp, vp, vp]),
+                                ("surfel_eval_mean_below", i, [ALLOC_FN, vp, i64, vp, f, vp, vp]),
+                                ("surfel_eval_dilate_masks", i, [ALLOC_FN, vp, i, i, i, vp, i, vp, vp]),
+                                ("surfel_eval_cull_vertices", i, [i64, vp, i, vp, i, i, vp, vp, vp])):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
