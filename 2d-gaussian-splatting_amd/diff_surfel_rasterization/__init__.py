@@ -121,7 +121,6 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
         rs = raster_settings
-        lib = _n.load()
         dev = means3D.device
         if dev.type != "cuda":
             raise RuntimeError("diff_surfel_rasterization: tensors must live on a HIP device (got %s)" % dev)
@@ -135,16 +134,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         out_others = torch.empty((7, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
         ga, ba, ia = _n.TorchAllocator(dev), _n.TorchAllocator(dev), _n.TorchAllocator(dev)
-        with torch.cuda.device(dev):
-            R = lib.surfel_rasterize_forward(ga.cb, None, ba.cb, None, ia.cb, None, P, int(rs.sh_degree), M, _n.ptr(bg), W, H,
-                                             _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp), _n.ptr(opacities),
-                                             _n.ptr(scales), float(rs.scale_modifier), _n.ptr(rotations),
-                                             _n.ptr(cov3Ds_precomp), _n.ptr(viewmatrix), _n.ptr(projmatrix), _n.ptr(campos),
-                                             float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)),
-                                             _n.ptr(out_color), _n.ptr(out_others), _n.ptr(radii), int(rs.debug),
-                                             _n.current_stream_ptr(dev))
-        if R < 0:
-            raise RuntimeError("surfel_rasterize_forward failed (%d): %s" % (R, _n.last_error()))
+        R = _n.call(dev, "surfel_rasterize_forward", ga.cb, None, ba.cb, None, ia.cb, None, P, int(rs.sh_degree), M, bg, W, H,
+                    means3D, sh, colors_precomp, opacities, scales, float(rs.scale_modifier), rotations, cov3Ds_precomp,
+                    viewmatrix, projmatrix, campos, float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)),
+                    out_color, out_others, radii, int(rs.debug))
         global last_num_rendered, _last_image
         last_num_rendered = int(R)
         _last_image = (ia.last(), (W + 15) // 16, (H + 15) // 16)
@@ -164,7 +157,6 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth):
         rs = ctx.raster_settings
-        lib = _n.load()
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, bg,
          viewmatrix, projmatrix, campos) = ctx.saved_tensors
         has_sh, has_col, has_sr, has_cov = ctx.has
@@ -198,20 +190,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         gc = grad_out_color.contiguous().float() if grad_out_color is not None else torch.zeros((3, H, W), device=dev)
         gd = grad_depth.contiguous().float() if grad_depth is not None else torch.zeros((7, H, W), device=dev)
         sa = _n.TorchAllocator(dev)
-        opt = lambda t, ok: _n.ptr(t) if ok else None
-        with torch.cuda.device(dev):
-            rc = lib.surfel_rasterize_backward(sa.cb, None, P, int(rs.sh_degree), M, ctx.num_rendered, _n.ptr(bg), W, H,
-                                               _n.ptr(means3D), opt(sh, has_sh), opt(colors_precomp, has_col),
-                                               opt(scales, has_sr), float(rs.scale_modifier), opt(rotations, has_sr),
-                                               opt(cov3Ds_precomp, has_cov), _n.ptr(viewmatrix), _n.ptr(projmatrix),
-                                               _n.ptr(campos), float(rs.tanfovx), float(rs.tanfovy), _n.ptr(radii),
-                                               _n.ptr(geomBuffer), _n.ptr(binningBuffer), _n.ptr(imgBuffer), _n.ptr(gc),
-                                               _n.ptr(gd), _n.ptr(g_means2D), _n.ptr(g_normal), _n.ptr(g_opac),
-                                               _n.ptr(g_colors), _n.ptr(g_means3D), _n.ptr(g_trans), _n.ptr(g_sh),
-                                               _n.ptr(g_scales), _n.ptr(g_rots), int(rs.debug),
-                                               _n.current_stream_ptr(dev))
-        if rc < 0:
-            raise RuntimeError("surfel_rasterize_backward failed (%d): %s" % (rc, _n.last_error()))
+        opt = lambda t, ok: t if ok else None
+        _n.call(dev, "surfel_rasterize_backward", sa.cb, None, P, int(rs.sh_degree), M, ctx.num_rendered, bg, W, H,
+                means3D, opt(sh, has_sh), opt(colors_precomp, has_col), opt(scales, has_sr), float(rs.scale_modifier),
+                opt(rotations, has_sr), opt(cov3Ds_precomp, has_cov), viewmatrix, projmatrix, campos, float(rs.tanfovx),
+                float(rs.tanfovy), radii, geomBuffer, binningBuffer, imgBuffer, gc, gd, g_means2D, g_normal, g_opac,
+                g_colors, g_means3D, g_trans, g_sh, g_scales, g_rots, int(rs.debug))
         return (g_means3D, g_means2D, g_sh, g_colors if has_col else None, g_opac, g_scales, g_rots,
                 g_trans if has_cov else None, None)
 
@@ -227,11 +211,7 @@ class GaussianRasterizer(nn.Module):
             positions = _c(positions)
             P = positions.shape[0]
             present = torch.zeros((P,), dtype=torch.uint8, device=positions.device)
-            with torch.cuda.device(positions.device):
-                rc = _n.load().surfel_mark_visible(P, _n.ptr(positions), _n.ptr(_c(rs.viewmatrix)), _n.ptr(_c(rs.projmatrix)),
-                                                   _n.ptr(present), _n.current_stream_ptr(positions.device))
-            if rc < 0:
-                raise RuntimeError("surfel_mark_visible failed: %s" % _n.last_error())
+            _n.call(positions.device, "surfel_mark_visible", P, positions, _c(rs.viewmatrix), _c(rs.projmatrix), present)
         return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

@@ -14,8 +14,5 @@ def distCUDA2(points):
     P = pts.shape[0]
     out = torch.empty((P,), dtype=torch.float32, device=pts.device)
     sa = _n.TorchAllocator(pts.device)
-    with torch.cuda.device(pts.device):
-        rc = _n.load().surfel_knn_dist2(sa.cb, None, P, _n.ptr(pts), _n.ptr(out), _n.current_stream_ptr(pts.device))
-    if rc < 0:
-        raise RuntimeError("surfel_knn_dist2 failed: %s" % _n.last_error())
+    _n.call(pts.device, "surfel_knn_dist2", sa.cb, None, P, pts, out)
     return out

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 import surfel_native as _n
-from surfel_mesh import MeshLimitError, TriangleMesh
+from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -42,32 +42,19 @@ def _points(t, what):
     return t.detach().to(torch.float32).contiguous()
 
 
-def _call(dev, what, fn, *args):
-    with torch.cuda.device(dev):
-        rc = fn(*args)
-    if rc == -4:
-        raise MeshLimitError("%s: %s" % (what, _n.last_error()))
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, _n.last_error()))
-    return rc
-
-
 # ------------------------------------------------------------------------------------------------ rule 1: sampling
 def sample_mesh(mesh, density, budget_bytes=DEFAULT_BUDGET, return_counts=False):
     """Points of a mesh as eval.py:48-71: every vertex, then the lattice samples of every triangle in triangle order -> [N, 3] float32.
     return_counts: also the samples per triangle [F] (int64).  MeshLimitError when the cloud would exceed budget_bytes."""
     verts = _points(mesh.vertices, "mesh.vertices")
     tris = _dev(mesh.triangles, "mesh.triangles").detach().to(torch.int32).contiguous()
-    dev, lib = verts.device, _n.load()
+    dev = verts.device
     V, F = verts.shape[0], tris.shape[0]
     alloc = _n.TorchAllocator(dev)
     offsets = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
-    s = _n.current_stream_ptr(dev)
-    total = _call(dev, "surfel_eval_sample_count", lib.surfel_eval_sample_count, alloc.cb, None, V, F, _n.ptr(verts), _n.ptr(tris), float(density),
-                  int(budget_bytes), _n.ptr(offsets), s)
+    total = _n.call(dev, "surfel_eval_sample_count", alloc.cb, None, V, F, verts, tris, float(density), int(budget_bytes), offsets)
     pts = torch.empty((V + total, 3), dtype=torch.float32, device=dev)
-    _call(dev, "surfel_eval_sample_emit", lib.surfel_eval_sample_emit, V, F, _n.ptr(verts), _n.ptr(tris), float(density), _n.ptr(offsets), total,
-          _n.ptr(pts), s)
+    _n.call(dev, "surfel_eval_sample_emit", V, F, verts, tris, float(density), offsets, total, pts)
     if not return_counts:
         return pts
     off = offsets[:F].to(torch.int64)
@@ -102,8 +89,7 @@ class Grid:
         self.g.cell = cell
         self.g.dims[:] = [int(x) for x in dims]
         self.g.budget_bytes = int(budget_bytes)
-        _call(self.device, "surfel_eval_grid_build", self.lib.surfel_eval_grid_build, self.alloc.cb, None, C.byref(self.g), n, _n.ptr(points),
-              _n.ptr(rank), _n.current_stream_ptr(self.device))
+        _n.call(self.device, "surfel_eval_grid_build", self.alloc.cb, None, self.g, n, points, rank)
 
 
 def shuffle_rank(n, seed, device):
@@ -135,8 +121,7 @@ def _thin(grid, density):
     dev, n = grid.device, grid.points.shape[0]
     keep = torch.zeros(n, dtype=torch.uint8, device=dev)
     rounds = C.c_int(0)
-    _call(dev, "surfel_eval_thin", grid.lib.surfel_eval_thin, grid.alloc.cb, None, C.byref(grid.g), float(np.float32(density)), _n.ptr(keep),
-          C.byref(rounds), _n.current_stream_ptr(dev))
+    _n.call(dev, "surfel_eval_thin", grid.alloc.cb, None, grid.g, float(np.float32(density)), keep, rounds)
     return keep.bool(), rounds.value
 
 
@@ -166,8 +151,7 @@ def _nearest(q, grid, max_dist, return_index=False):
     dist = torch.empty(q.shape[0], dtype=torch.float32, device=dev)
     idx = torch.empty(q.shape[0], dtype=torch.int32, device=dev) if return_index else None
     alloc = _n.TorchAllocator(dev)
-    _call(dev, "surfel_eval_nearest", grid.lib.surfel_eval_nearest, alloc.cb, None, C.byref(grid.g), q.shape[0], _n.ptr(q), float(max_dist), _n.ptr(dist),
-          _n.ptr(idx), _n.current_stream_ptr(dev))
+    _n.call(dev, "surfel_eval_nearest", alloc.cb, None, grid.g, q.shape[0], q, float(max_dist), dist, idx)
     return (dist, idx) if return_index else dist
 
 
@@ -177,8 +161,7 @@ def sum_count_below(dist, bound):
     dev = d.device
     out = torch.empty(2, dtype=torch.float64, device=dev)
     alloc = _n.TorchAllocator(dev)
-    _call(dev, "surfel_eval_mean_below", _n.load().surfel_eval_mean_below, alloc.cb, None, d.shape[0], _n.ptr(d), float(bound), _n.ptr(out),
-          _n.current_stream_ptr(dev))
+    _n.call(dev, "surfel_eval_mean_below", alloc.cb, None, d.shape[0], d, float(bound), out)
     s, c = out.cpu().tolist()
     return s, int(c)
 
@@ -224,7 +207,7 @@ def evaluate_dtu(data, stl, obs_mask, bb, res, plane, *, mode="mesh", density=0.
     if mode not in ("mesh", "pcd"):
         raise ValueError("surfel_eval: mode must be 'mesh' or 'pcd', got %r" % (mode,))
     stl = _points(stl, "stl")
-    dev, lib = stl.device, _n.load()
+    dev = stl.device
     obs_mask = _dev(obs_mask, "obs_mask")
     if obs_mask.ndim != 3:
         raise ValueError("surfel_eval: obs_mask must be [X, Y, Z]")
@@ -241,18 +224,16 @@ def evaluate_dtu(data, stl, obs_mask, bb, res, plane, *, mode="mesh", density=0.
     laps.lap("thin")
     data_down = data_pcd[keep]
     n = data_down.shape[0]
-    s = _n.current_stream_ptr(dev)
     inbound = torch.zeros(n, dtype=torch.uint8, device=dev)
     in_obs = torch.zeros(n, dtype=torch.uint8, device=dev)
     bbf = (C.c_float * 6)(*[float(x) for x in np.asarray(bb, np.float32).reshape(-1)[:6]])
     dims = (C.c_int * 3)(*obs_mask.shape)
-    _call(dev, "surfel_eval_obs_mask", lib.surfel_eval_obs_mask, n, _n.ptr(data_down), bbf, float(patch), float(np.asarray(res, np.float64).reshape(-1)[0]),
-          _n.ptr(obs_mask), dims, _n.ptr(inbound), _n.ptr(in_obs), s)
+    _n.call(dev, "surfel_eval_obs_mask", n, data_down, bbf, float(patch), float(np.asarray(res, np.float64).reshape(-1)[0]), obs_mask, dims, inbound, in_obs)
     inbound, in_obs = inbound.bool(), in_obs.bool()
     data_in, data_in_obs = data_down[inbound], data_down[in_obs]
     above = torch.zeros(stl.shape[0], dtype=torch.uint8, device=dev)
     pl = (C.c_double * 4)(*[float(x) for x in np.asarray(plane, np.float64).reshape(-1)[:4]])
-    _call(dev, "surfel_eval_above_plane", lib.surfel_eval_above_plane, stl.shape[0], _n.ptr(stl), pl, _n.ptr(above), s)
+    _n.call(dev, "surfel_eval_above_plane", stl.shape[0], stl, pl, above)
     above = above.bool()
     stl_above = stl[above]
     laps.lap("mask")
@@ -311,8 +292,7 @@ def dilate_masks(masks, radius=24):
     m = m.contiguous()
     out = torch.empty_like(m)
     alloc = _n.TorchAllocator(m.device)
-    _call(m.device, "surfel_eval_dilate_masks", _n.load().surfel_eval_dilate_masks, alloc.cb, None, m.shape[0], m.shape[1], m.shape[2], _n.ptr(m),
-          int(radius), _n.ptr(out), _n.current_stream_ptr(m.device))
+    _n.call(m.device, "surfel_eval_dilate_masks", alloc.cb, None, m.shape[0], m.shape[1], m.shape[2], m, int(radius), out)
     return out
 
 
@@ -324,8 +304,7 @@ def cull_vertices(vertices, proj, dilated):
     if d.ndim != 3 or d.dtype != torch.uint8 or d.shape[0] != p.shape[0]:
         raise ValueError("surfel_eval: dilated must be uint8 [V, H, W] with one view per projection")
     keep = torch.zeros(v.shape[0], dtype=torch.uint8, device=v.device)
-    _call(v.device, "surfel_eval_cull_vertices", _n.load().surfel_eval_cull_vertices, v.shape[0], _n.ptr(v), p.shape[0], _n.ptr(p), d.shape[1], d.shape[2],
-          _n.ptr(d), _n.ptr(keep), _n.current_stream_ptr(v.device))
+    _n.call(v.device, "surfel_eval_cull_vertices", v.shape[0], v, p.shape[0], p, d.shape[1], d.shape[2], d, keep)
     return keep.bool()
 
 

@@ -12,12 +12,6 @@ import surfel_native as _n
 _n.load()
 
 
-def _check(rc, what):
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, _n.last_error()))
-    return rc
-
-
 def _planes(img, gt):
     if img.shape != gt.shape or img.dim() < 2:
         raise ValueError("image / target shapes differ: %s vs %s" % (tuple(img.shape), tuple(gt.shape)))
@@ -36,17 +30,12 @@ class _L1SSIM(torch.autograd.Function):
         x = img.detach().contiguous().float(); y = gt.detach().contiguous().float()
         dev = x.device
         need = img.requires_grad
-        lib = _n.load()
         nblk = ((W + 31) // 32) * ((H + 31) // 32)
         dmaps = torch.empty((3, planes, H, W), dtype=torch.float32, device=dev) if need else None
         partials = torch.empty((planes * nblk, 2), dtype=torch.float32, device=dev)
         out = torch.empty((2,), dtype=torch.float32, device=dev)
-        s = _n.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            _check(lib.surfel_l1_ssim_forward_w(int(window), planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), s),
-                   "surfel_l1_ssim_forward")
-            _check(lib.surfel_reduce_partials(_n.ptr(partials), 1, planes * nblk, 2, 1.0 / (planes * H * W), _n.ptr(out), s),
-                   "surfel_reduce_partials")
+        _n.call(dev, "surfel_l1_ssim_forward_w", int(window), planes, H, W, x, y, dmaps, partials)
+        _n.call(dev, "surfel_reduce_partials", partials, 1, planes * nblk, 2, 1.0 / (planes * H * W), out)
         ctx.dims = (planes, H, W)
         ctx.window = int(window)
         ctx.in_shape = tuple(img.shape)
@@ -58,14 +47,10 @@ class _L1SSIM(torch.autograd.Function):
     def backward(ctx, g):
         planes, H, W = ctx.dims
         x, y, dmaps = ctx.saved_tensors
-        dev = x.device
-        lib = _n.load()
         N = float(planes * H * W)
         g = g.contiguous().float()          # (dL/d mean|.|, dL/d mean S), stays on the device
         grad = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            _check(lib.surfel_l1_ssim_backward_w(ctx.window, planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), 1.0 / N, 1.0 / N, _n.ptr(g[0:1]),
-                                                 _n.ptr(g[1:2]), _n.ptr(grad), _n.current_stream_ptr(dev)), "surfel_l1_ssim_backward")
+        _n.call(x.device, "surfel_l1_ssim_backward_w", ctx.window, planes, H, W, x, y, dmaps, 1.0 / N, 1.0 / N, g[0:1], g[1:2], grad)
         return grad.view(ctx.in_shape), None, None
 
 
@@ -87,13 +72,10 @@ class _SSIMPerImage(torch.autograd.Function):
         B, C, H, W = (int(v) for v in img.shape)
         x = img.detach().contiguous().float(); y = gt.detach().contiguous().float()
         dev = x.device
-        lib = _n.load()
         nblk = ((W + 31) // 32) * ((H + 31) // 32)
         dmaps = torch.empty((3, B * C, H, W), dtype=torch.float32, device=dev)
         partials = torch.empty((B * C * nblk, 2), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib.surfel_l1_ssim_forward_w(int(window), B * C, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials),
-                                                _n.current_stream_ptr(dev)), "surfel_l1_ssim_forward")
+        _n.call(dev, "surfel_l1_ssim_forward_w", int(window), B * C, H, W, x, y, dmaps, partials)
         ctx.dims = (B, C, H, W)
         ctx.window = int(window)
         ctx.save_for_backward(x, y, dmaps)
@@ -103,16 +85,11 @@ class _SSIMPerImage(torch.autograd.Function):
     def backward(ctx, g):
         B, C, H, W = ctx.dims
         x, y, dmaps = ctx.saved_tensors
-        dev = x.device
-        lib = _n.load()
         g = g.contiguous().float()
         grad = torch.empty_like(x)
-        s = _n.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            for b in range(B):        # one launch per batch element: its own upstream scalar
-                dm = dmaps[:, b * C:(b + 1) * C].contiguous()
-                _check(lib.surfel_l1_ssim_backward_w(ctx.window, C, H, W, _n.ptr(x[b]), _n.ptr(y[b]), _n.ptr(dm), 0.0, 1.0 / float(C * H * W), None,
-                                                     _n.ptr(g[b:b + 1]), _n.ptr(grad[b]), s), "surfel_l1_ssim_backward")
+        for b in range(B):        # one launch per batch element: its own upstream scalar
+            dm = dmaps[:, b * C:(b + 1) * C].contiguous()
+            _n.call(x.device, "surfel_l1_ssim_backward_w", ctx.window, C, H, W, x[b], y[b], dm, 0.0, 1.0 / float(C * H * W), None, g[b:b + 1], grad[b])
         return grad, None, None
 
 
@@ -140,16 +117,12 @@ class _PhotometricLoss(torch.autograd.Function):
         planes, H, W = _planes(img, gt)
         x = img.detach().contiguous().float(); y = gt.detach().contiguous().float()
         dev = x.device
-        lib = _n.load()
         nblk = ((W + 31) // 32) * ((H + 31) // 32)
         dmaps = torch.empty((3, planes, H, W), dtype=torch.float32, device=dev)
         partials = torch.empty((planes * nblk, 2), dtype=torch.float32, device=dev)
         means = torch.empty((2,), dtype=torch.float32, device=dev)
-        s = _n.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            _check(lib.surfel_l1_ssim_forward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), s), "surfel_l1_ssim_forward")
-            _check(lib.surfel_reduce_partials(_n.ptr(partials), 1, planes * nblk, 2, 1.0 / (planes * H * W), _n.ptr(means), s),
-                   "surfel_reduce_partials")
+        _n.call(dev, "surfel_l1_ssim_forward", planes, H, W, x, y, dmaps, partials)
+        _n.call(dev, "surfel_reduce_partials", partials, 1, planes * nblk, 2, 1.0 / (planes * H * W), means)
         ctx.dims = (planes, H, W, float(lambda_dssim))
         ctx.in_shape = tuple(img.shape)
         ctx.save_for_backward(x, y, dmaps)
@@ -161,13 +134,10 @@ class _PhotometricLoss(torch.autograd.Function):
     def backward(ctx, g_loss, g_means):
         planes, H, W, lam = ctx.dims
         x, y, dmaps = ctx.saved_tensors
-        dev = x.device
         N = float(planes * H * W)
         grad = torch.empty_like(x)
         g = g_loss.contiguous().float().reshape(1)
-        with torch.cuda.device(dev):
-            _check(_n.load().surfel_l1_ssim_backward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), (1.0 - lam) / N, -lam / N, _n.ptr(g),
-                                                     _n.ptr(g), _n.ptr(grad), _n.current_stream_ptr(dev)), "surfel_l1_ssim_backward")
+        _n.call(x.device, "surfel_l1_ssim_backward", planes, H, W, x, y, dmaps, (1.0 - lam) / N, -lam / N, g, g, grad)
         return grad.view(ctx.in_shape), None, None
 
 
@@ -182,7 +152,7 @@ def photometric_loss(image, gt_image, lambda_dssim=0.2):
 FUSED_LOSS = True
 
 
-def _loss_forward(lib, planes, H, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg, s):
+def _loss_forward(planes, H, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg):
     """L1 + SSIM partial sums into `partials` [+ the regularisers' per-16x16-block sums]; returns (allmap as fp32, those sums) or
     (None, None) without regularisers.  Both halves in one launch where FUSED_LOSS allows: they share no data, their workgroups run
     side by side."""
@@ -191,18 +161,16 @@ def _loss_forward(lib, planes, H, W, x, y, dmaps, partials, allmap, cam, depth_r
         am = allmap.detach().contiguous().float()
         pb = torch.empty((((W + 15) // 16) * ((H + 15) // 16), 2), dtype=torch.float32, device=x.device)
     if reg and planes == 3 and FUSED_LOSS:
-        _check(lib.surfel_train_loss_forward(H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), _n.ptr(am), _n.ptr(cam),
-                                             float(depth_ratio), _n.ptr(pb), s), "surfel_train_loss_forward")
+        _n.call(x.device, "surfel_train_loss_forward", H, W, x, y, dmaps, partials, am, cam, float(depth_ratio), pb)
     else:
-        _check(lib.surfel_l1_ssim_forward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), _n.ptr(partials), s), "surfel_l1_ssim_forward")
+        _n.call(x.device, "surfel_l1_ssim_forward", planes, H, W, x, y, dmaps, partials)
         if reg:
             # maps = NULL: only the two regulariser sums are needed (the backward recomputes from allmap)
-            _check(lib.surfel_render_post_forward(H, W, _n.ptr(am), _n.ptr(cam), float(depth_ratio), None, _n.ptr(pb), s),
-                   "surfel_render_post_forward")
+            _n.call(x.device, "surfel_render_post_forward", H, W, am, cam, float(depth_ratio), None, pb)
     return am, pb
 
 
-def _loss_backward(lib, planes, H, W, x, y, dmaps, am, cam, ratio, weights, g, fin, s):
+def _loss_backward(planes, H, W, x, y, dmaps, am, cam, ratio, weights, g, fin):
     """dL/dimage and dL/dallmap (None without regularisers: am is None) for the loss weights (L1, SSIM, normal, distortion) of
     the pixel means, scaled by the upstream scalar g.  fin = (partials, regulariser sums, lambda_dssim, lambda_normal,
     lambda_dist, scalars out, total out): the fused launch's optional finalize workgroup (null pointers: none)."""
@@ -210,15 +178,11 @@ def _loss_backward(lib, planes, H, W, x, y, dmaps, am, cam, ratio, weights, g, f
     grad_img = torch.empty_like(x)
     grad_am = None if am is None else torch.empty_like(am)
     if am is not None and planes == 3 and FUSED_LOSS:
-        _check(lib.surfel_train_loss_backward(H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), w_l1, w_ssim, _n.ptr(am), _n.ptr(cam), ratio, w_n, w_d,
-                                              _n.ptr(g), _n.ptr(grad_img), _n.ptr(grad_am), _n.ptr(fin[0]), _n.ptr(fin[1]), fin[2], fin[3], fin[4],
-                                              _n.ptr(fin[5]), _n.ptr(fin[6]), s), "surfel_train_loss_backward")
+        _n.call(x.device, "surfel_train_loss_backward", H, W, x, y, dmaps, w_l1, w_ssim, am, cam, ratio, w_n, w_d, g, grad_img, grad_am, *fin)
     else:
-        _check(lib.surfel_l1_ssim_backward(planes, H, W, _n.ptr(x), _n.ptr(y), _n.ptr(dmaps), w_l1, w_ssim, _n.ptr(g), _n.ptr(g),
-                                           _n.ptr(grad_img), s), "surfel_l1_ssim_backward")
+        _n.call(x.device, "surfel_l1_ssim_backward", planes, H, W, x, y, dmaps, w_l1, w_ssim, g, g, grad_img)
         if am is not None:
-            _check(lib.surfel_render_post_backward(H, W, _n.ptr(am), _n.ptr(cam), ratio, None, w_n, w_d, _n.ptr(g), _n.ptr(grad_am), s),
-                   "surfel_render_post_backward")
+            _n.call(x.device, "surfel_render_post_backward", H, W, am, cam, ratio, None, w_n, w_d, g, grad_am)
     return grad_img, grad_am
 
 
@@ -242,25 +206,21 @@ class _TrainLoss(torch.autograd.Function):
         planes, H, W = _planes(image, gt)
         x = image.detach().contiguous().float(); y = gt.detach().contiguous().float()
         dev = x.device
-        lib = _n.load()
         reg = (lambda_normal != 0.0 or lambda_dist != 0.0) and allmap is not None
         nblk = ((W + 31) // 32) * ((H + 31) // 32)
         dmaps = torch.empty((3, planes, H, W), dtype=torch.float32, device=dev)
         partials = torch.empty((planes * nblk, 2), dtype=torch.float32, device=dev)
         out = torch.empty((6,), dtype=torch.float32, device=dev)
         total = torch.empty((), dtype=torch.float32, device=dev)
-        s = _n.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            am, pb = _loss_forward(lib, planes, H, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg, s)
-            # defer_scalars: the loss scalars are written by an extra workgroup of the fused BACKWARD launch (valid once the backward has
-            # run: a training loop reads them after the step) — one launch less per iteration
-            ctx.deferred = None
-            if defer_scalars and reg and planes == 3 and FUSED_LOSS and (image.requires_grad or getattr(ctx, "manual", False)):
-                ctx.deferred = (partials, pb, out, total)
-            else:
-                _check(lib.surfel_loss_finalize(_n.ptr(partials), planes * nblk, planes * H * W, _n.ptr(pb), 0 if pb is None else pb.shape[0], H * W,
-                                                float(lambda_dssim), float(lambda_normal) if reg else 0.0, float(lambda_dist) if reg else 0.0,
-                                                _n.ptr(out), _n.ptr(total), s), "surfel_loss_finalize")
+        am, pb = _loss_forward(planes, H, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg)
+        # defer_scalars: the loss scalars are written by an extra workgroup of the fused BACKWARD launch (valid once the backward has
+        # run: a training loop reads them after the step) — one launch less per iteration
+        ctx.deferred = None
+        if defer_scalars and reg and planes == 3 and FUSED_LOSS and (image.requires_grad or getattr(ctx, "manual", False)):
+            ctx.deferred = (partials, pb, out, total)
+        else:
+            _n.call(dev, "surfel_loss_finalize", partials, planes * nblk, planes * H * W, pb, 0 if pb is None else pb.shape[0], H * W,
+                    float(lambda_dssim), float(lambda_normal) if reg else 0.0, float(lambda_dist) if reg else 0.0, out, total)
         ctx.set_materialize_grads(False)
         ctx.k = (planes, H, W, float(depth_ratio), float(lambda_dssim), float(lambda_normal), float(lambda_dist))
         ctx.shapes = (tuple(image.shape), None if allmap is None else tuple(allmap.shape))
@@ -274,14 +234,11 @@ class _TrainLoss(torch.autograd.Function):
         x, y, dmaps, am, cam = ctx.saved_tensors
         if g_total is None:
             return None, None, None, None, None, None, None, None, None
-        dev = x.device
         N = float(planes * H * W)
         g = g_total.contiguous().float().reshape(1)
         d = ctx.deferred or (None, None, None, None)
-        with torch.cuda.device(dev):
-            grad_img, grad_am = _loss_backward(_n.load(), planes, H, W, x, y, dmaps, am, cam, ratio,
-                                               ((1.0 - lam) / N, -lam / N, ln / (H * W), ld / (H * W)), g,
-                                               (d[0], d[1], lam, ln, ld, d[2], d[3]), _n.current_stream_ptr(dev))
+        grad_img, grad_am = _loss_backward(planes, H, W, x, y, dmaps, am, cam, ratio, ((1.0 - lam) / N, -lam / N, ln / (H * W), ld / (H * W)), g,
+                                           (d[0], d[1], lam, ln, ld, d[2], d[3]))
         return grad_img.view(ctx.shapes[0]), grad_am, None, None, None, None, None, None, None
 
 
@@ -333,8 +290,7 @@ class _TrainLossBand(torch.autograd.Function):
         nbx, nby = (W + 31) // 32, (He + 31) // 32
         dmaps = torch.empty((3, planes, He, W), dtype=torch.float32, device=dev)
         partials = torch.empty((planes * nbx * nby, 2), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            am, pb = _loss_forward(_n.load(), planes, He, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg, _n.current_stream_ptr(dev))
+        am, pb = _loss_forward(planes, He, W, x, y, dmaps, partials, allmap, cam, depth_ratio, reg)
         sums = torch.zeros((4,), dtype=torch.float32, device=dev)
         sums[0:2] = partials.view(planes, nby, nbx, 2)[:, a // 32:(b + 31) // 32].sum((0, 1, 2))
         if reg:
@@ -354,11 +310,9 @@ class _TrainLossBand(torch.autograd.Function):
         x, y, dmaps, am, cam = ctx.saved_tensors
         if g_share is None:
             return (None,) * 10
-        dev = x.device
         g = g_share.contiguous().float().reshape(1)
-        with torch.cuda.device(dev):
-            grad_img, grad_am = _loss_backward(_n.load(), planes, He, W, x, y, dmaps, am, cam, ratio, ((1.0 - lam) / N3, -lam / N3, ln / N1, ld / N1),
-                                               g, (None, None, 0.0, 0.0, 0.0, None, None), _n.current_stream_ptr(dev))
+        grad_img, grad_am = _loss_backward(planes, He, W, x, y, dmaps, am, cam, ratio, ((1.0 - lam) / N3, -lam / N3, ln / N1, ld / N1), g,
+                                           (None, None, 0.0, 0.0, 0.0, None, None))
         return (grad_img.view(ctx.shapes[0]), grad_am) + (None,) * 8
 
 

@@ -22,14 +22,7 @@ import surfel_native as _n
 _n.load()
 
 
-def _check(rc, what):
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, _n.last_error()))
-    return rc
-
-
-class MeshLimitError(RuntimeError):
-    """SURFEL_E_LIMIT: the volume would exceed the byte budget (raise the budget or the voxel size)."""
+MeshLimitError = _n.LimitError      # SURFEL_E_LIMIT: the volume would exceed the byte budget (raise the budget or the voxel size)
 
 
 class TriangleMesh:
@@ -84,45 +77,31 @@ class TsdfVolume:
         self.v.origin[:] = [int(x) for x in origin]
         self.v.dims[:] = [int(x) for x in dims]
         self.v.voxel_size, self.v.sdf_trunc, self.v.budget_bytes = float(voxel_size), float(sdf_trunc), int(budget_bytes)
-        self._call("surfel_tsdf_init", self.lib.surfel_tsdf_init, C.byref(self.v), self.alloc.cb, None, self._s())
-
-    def _s(self):
-        return _n.current_stream_ptr(self.device)
-
-    def _call(self, what, fn, *args):
-        with torch.cuda.device(self.device):
-            rc = fn(*args)
-        if rc == -4:
-            raise MeshLimitError("%s: %s" % (what, _n.last_error()))
-        return _check(rc, what)
+        _n.call(self.device, "surfel_tsdf_init", self.v, self.alloc.cb, None)
 
     def mark(self, depth, cam):
         H, W = depth.shape[-2:]
-        self._call("surfel_tsdf_mark", self.lib.surfel_tsdf_mark, C.byref(self.v), H, W, _n.ptr(depth), _n.ptr(cam), self._s())
+        _n.call(self.device, "surfel_tsdf_mark", self.v, H, W, depth, cam)
 
     def allocate(self):
-        return self._call("surfel_tsdf_allocate", self.lib.surfel_tsdf_allocate, C.byref(self.v), self.alloc.cb, None, self._s())
+        return _n.call(self.device, "surfel_tsdf_allocate", self.v, self.alloc.cb, None)
 
     def integrate(self, depth, rgba, cam):
         H, W = depth.shape[-2:]
-        self._call("surfel_tsdf_integrate", self.lib.surfel_tsdf_integrate, C.byref(self.v), H, W, _n.ptr(depth), _n.ptr(rgba), _n.ptr(cam), self._s())
+        _n.call(self.device, "surfel_tsdf_integrate", self.v, H, W, depth, rgba, cam)
 
     def extract(self):
-        self._call("surfel_tsdf_count", self.lib.surfel_tsdf_count, C.byref(self.v), self._s())
+        _n.call(self.device, "surfel_tsdf_count", self.v)
         V, F = int(self.v.nverts), int(self.v.ntris)
         verts = torch.empty((V, 3), dtype=torch.float32, device=self.device)
         cols = torch.empty((V, 3), dtype=torch.float32, device=self.device)
         tris = torch.empty((F, 3), dtype=torch.int32, device=self.device)
-        self._call("surfel_tsdf_extract", self.lib.surfel_tsdf_extract, C.byref(self.v), _n.ptr(verts), _n.ptr(cols), _n.ptr(tris), self._s())
+        _n.call(self.device, "surfel_tsdf_extract", self.v, verts, cols, tris)
         return TriangleMesh(verts, tris, cols)
 
     def _tensor(self, field, dtype, shape):
         """A view of one of the library's buffers (white-box access for tests and measurement)."""
-        p = getattr(self.v, field)
-        for t in self.alloc.held:
-            if t.data_ptr() == p:
-                return t[:int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(*shape)
-        raise KeyError(field)
+        return self.alloc.view(getattr(self.v, field), dtype, shape)
 
     def blocks(self):
         """(block coordinates [nblocks,3] int64 in slot order = table order, tsdf_rgb [nblocks,4096,4], weight [nblocks,4096])"""
@@ -199,9 +178,7 @@ def prepare_view(surf_depth, rgb, mask, depth_trunc):
     m = None if mask is None else mask.detach().contiguous().float().to(d.device)
     dout = torch.empty((H, W), dtype=torch.float32, device=d.device)
     rgba = torch.empty((H, W), dtype=torch.int32, device=d.device)
-    with torch.cuda.device(d.device):
-        _check(_n.load().surfel_mesh_prepare_view(H, W, _n.ptr(d), _n.ptr(rgb), _n.ptr(m), float(depth_trunc), _n.ptr(dout), _n.ptr(rgba),
-                                                  _n.current_stream_ptr(d.device)), "surfel_mesh_prepare_view")
+    _n.call(d.device, "surfel_mesh_prepare_view", H, W, d, rgb, m, float(depth_trunc), dout, rgba)
     return dout, rgba
 
 
@@ -258,38 +235,25 @@ class UnboundedLattice:
         self.v.M, self.v.slab, self.v.R = int(M), int(slab), float(R)
         self.v.center[:] = [float(x) for x in np.asarray(center.detach().cpu().numpy() if torch.is_tensor(center) else center, np.float64)]
         self.v.radius, self.v.voxel_size, self.v.budget_bytes = float(radius), float(voxel_size), int(budget_bytes)
-        self._call("surfel_unbounded_init", self.lib.surfel_unbounded_init, C.byref(self.v), self.alloc.cb, None, self._s())
-
-    def _s(self):
-        return _n.current_stream_ptr(self.device)
-
-    def _call(self, what, fn, *args):
-        with torch.cuda.device(self.device):
-            rc = fn(*args)
-        if rc == -4:
-            raise MeshLimitError("%s: %s" % (what, _n.last_error()))
-        return _check(rc, what)
+        _n.call(self.device, "surfel_unbounded_init", self.v, self.alloc.cb, None)
 
     def fuse(self, views, depth, count=None):
         """views / depth from pack_views; count: a uint16-sized tensor [M^3] (int16 storage) that receives every sample's view count."""
         n = views.numel() // 64
-        self._call("surfel_unbounded_fuse", self.lib.surfel_unbounded_fuse, C.byref(self.v), n, _n.ptr(views), _n.ptr(depth), _n.ptr(count), self._s())
+        _n.call(self.device, "surfel_unbounded_fuse", self.v, n, views, depth, count)
 
     def tsdf(self):
         """The lattice [M, M, M] indexed [z, y, x] (a view of the library's buffer)."""
         M = self.v.M
-        for t in self.alloc.held:
-            if t.data_ptr() == self.v.tsdf:
-                return t[:4 * M ** 3].view(torch.float32).view(M, M, M)
-        raise KeyError("tsdf")
+        return self.alloc.view(self.v.tsdf, torch.float32, (M, M, M))
 
     def extract(self):
         """(verts [V,3] world, clipped to +-32, tris [F,3] int32) in lattice / cube order."""
-        self._call("surfel_unbounded_count", self.lib.surfel_unbounded_count, C.byref(self.v), self._s())
+        _n.call(self.device, "surfel_unbounded_count", self.v)
         V, F = int(self.v.nverts), int(self.v.ntris)
         verts = torch.empty((V, 3), dtype=torch.float32, device=self.device)
         tris = torch.empty((F, 3), dtype=torch.int32, device=self.device)
-        self._call("surfel_unbounded_extract", self.lib.surfel_unbounded_extract, C.byref(self.v), _n.ptr(verts), _n.ptr(tris), self._s())
+        _n.call(self.device, "surfel_unbounded_extract", self.v, verts, tris)
         return verts, tris
 
 
@@ -297,9 +261,7 @@ def color_vertices(verts, views, depth, rgb, sdf_trunc):
     """colors [V,3] = sum of bilinear rgb / (1 + n) over the views that see a vertex within sdf_trunc (surfel_unbounded_color)."""
     V = int(verts.shape[0])
     cols = torch.empty((V, 3), dtype=torch.float32, device=verts.device)
-    with torch.cuda.device(verts.device):
-        _check(_n.load().surfel_unbounded_color(V, _n.ptr(verts.contiguous()), views.numel() // 64, _n.ptr(views), _n.ptr(depth), _n.ptr(rgb),
-                                                float(sdf_trunc), _n.ptr(cols), _n.current_stream_ptr(verts.device)), "surfel_unbounded_color")
+    _n.call(verts.device, "surfel_unbounded_color", V, verts.contiguous(), views.numel() // 64, views, depth, rgb, float(sdf_trunc), cols)
     return cols
 
 
@@ -392,9 +354,7 @@ def cluster_triangles(mesh):
     label = torch.empty(F, dtype=torch.int32, device=tris.device)
     size = torch.empty(F, dtype=torch.int32, device=tris.device)
     alloc = _n.TorchAllocator(tris.device)
-    with torch.cuda.device(tris.device):
-        _check(_n.load().surfel_mesh_clusters(alloc.cb, None, V, F, _n.ptr(tris), _n.ptr(label), _n.ptr(size), _n.current_stream_ptr(tris.device)),
-               "surfel_mesh_clusters")
+    _n.call(tris.device, "surfel_mesh_clusters", alloc.cb, None, V, F, tris, label, size)
     return label, size
 
 
@@ -415,10 +375,8 @@ def post_process_mesh(mesh, cluster_to_keep=1000):
     tout = torch.empty((F, 3), dtype=torch.int32, device=dev)
     n = (C.c_int64 * 2)()
     alloc = _n.TorchAllocator(dev)
-    with torch.cuda.device(dev):
-        _check(_n.load().surfel_mesh_filter(alloc.cb, None, V, F, _n.ptr(mesh.vertices.contiguous()), _n.ptr(mesh.vertex_colors.contiguous()),
-                                            _n.ptr(mesh.triangles.contiguous()), _n.ptr(label), _n.ptr(size), threshold, _n.ptr(vout), _n.ptr(cout),
-                                            _n.ptr(tout), n, _n.current_stream_ptr(dev)), "surfel_mesh_filter")
+    _n.call(dev, "surfel_mesh_filter", alloc.cb, None, V, F, mesh.vertices.contiguous(), mesh.vertex_colors.contiguous(), mesh.triangles.contiguous(),
+            label, size, threshold, vout, cout, tout, n)
     print("num vertices raw {}".format(V))
     print("num vertices post {}".format(int(n[0])))
     return TriangleMesh(vout[:n[0]], tout[:n[1]], cout[:n[0]])

@@ -190,10 +190,7 @@ class GaussianModel:
         """act = sigmoid(opacity) | exp(scaling) | normalize(rotation) (scene/gaussian_model.py:95-115) — one HIP launch."""
         if self.device.type != "cuda":
             raise RuntimeError("GaussianModel: the parameter store must live on a HIP device (no CPU path)")
-        with torch.cuda.device(self.device):
-            rc = _n.load().surfel_activate(self.P, _n.ptr(self.theta), _n.ptr(self.act), _n.current_stream_ptr(self.device))
-        if rc < 0:
-            raise RuntimeError("surfel_activate failed: %s" % _n.last_error())
+        _n.call(self.device, "surfel_activate", self.P, self.theta, self.act)
 
     # raw parameter views (the reference's nn.Parameters)
     @property
@@ -317,12 +314,8 @@ class GaussianModel:
         if colour_grads is not None:
             cam, gc = colour_grads[0].contiguous().float(), colour_grads[1].contiguous().float()
             N = int(gc.shape[0])
-        with torch.cuda.device(self.device):
-            rc = _n.load().surfel_adam_step(self.P, _n.ptr(self.theta), _n.ptr(self.grad), _n.ptr(self.m), _n.ptr(self.v), _n.ptr(self.act),
-                                            lr, self.betas[0], self.betas[1], self.eps, self.step_count, float(grad_scale),
-                                            int(self.active_sh_degree), N, _n.ptr(cam), _n.ptr(gc), int(parts), _n.current_stream_ptr(self.device))
-        if rc < 0:
-            raise RuntimeError("surfel_adam_step failed: %s" % _n.last_error())
+        _n.call(self.device, "surfel_adam_step", self.P, self.theta, self.grad, self.m, self.v, self.act, lr, self.betas[0], self.betas[1], self.eps,
+                self.step_count, float(grad_scale), int(self.active_sh_degree), N, cam, gc, int(parts))
 
     def update_step(self, colour_grads, stats=None, grad_scale=1.0):
         """add_densification_stats + optimizer_step(parts=3) as ONE launch (surfel_train_update) for the iterations in which nothing is
@@ -334,14 +327,9 @@ class GaussianModel:
         g = r = None
         if stats is not None:
             g, r = stats[0].contiguous().float(), stats[1].contiguous().to(torch.int32)
-        with torch.cuda.device(self.device):
-            rc = _n.load().surfel_train_update(self.P, _n.ptr(self.theta), _n.ptr(self.grad), _n.ptr(self.m), _n.ptr(self.v), _n.ptr(self.act),
-                                               lr, self.betas[0], self.betas[1], self.eps, self.step_count, float(grad_scale),
-                                               int(self.active_sh_degree), int(gc.shape[0]), _n.ptr(cam), _n.ptr(gc), _n.ptr(g), _n.ptr(r),
-                                               _n.ptr(self.xyz_gradient_accum), _n.ptr(self.denom), _n.ptr(self.max_radii2D),
-                                               _n.current_stream_ptr(self.device))
-        if rc < 0:
-            raise RuntimeError("surfel_train_update failed: %s" % _n.last_error())
+        _n.call(self.device, "surfel_train_update", self.P, self.theta, self.grad, self.m, self.v, self.act, lr, self.betas[0], self.betas[1], self.eps,
+                self.step_count, float(grad_scale), int(self.active_sh_degree), int(gc.shape[0]), cam, gc, g, r,
+                self.xyz_gradient_accum, self.denom, self.max_radii2D)
 
     def exchange_gradients(self, campos_all, group=None):
         """View-parallel step: make self.grad the SUM over ranks of the per-view gradients with
@@ -357,11 +345,7 @@ class GaussianModel:
         c = campos_all.contiguous().float(); g = gcol_all.contiguous().float()
         if g.untyped_storage().data_ptr() == self.grad.untyped_storage().data_ptr():
             g = g.clone()        # the fused-mode colour block lives inside the SH section this call overwrites
-        with torch.cuda.device(self.device):
-            rc = _n.load().surfel_sh_grad_gather(self.P, int(self.active_sh_degree), int(g.shape[0]), _n.ptr(self._pv["xyz"]), _n.ptr(c),
-                                                 _n.ptr(g), _n.ptr(self._gv["sh"]), _n.current_stream_ptr(self.device))
-        if rc < 0:
-            raise RuntimeError("surfel_sh_grad_gather failed: %s" % _n.last_error())
+        _n.call(self.device, "surfel_sh_grad_gather", self.P, int(self.active_sh_degree), int(g.shape[0]), self._pv["xyz"], c, g, self._gv["sh"])
 
     # ------------------------------------------------------------------ densification (scene/gaussian_model.py:257-407)
     def add_densification_stats(self, viewspace_point_tensor, update_filter=None, radii=None):
@@ -372,11 +356,7 @@ class GaussianModel:
         if radii is None:
             raise ValueError("add_densification_stats needs the view's radii (visibility = radii > 0)")
         g = g.contiguous().float(); r = radii.contiguous().to(torch.int32)
-        with torch.cuda.device(self.device):
-            rc = _n.load().surfel_densify_stats(self.P, _n.ptr(g), _n.ptr(r), _n.ptr(self.xyz_gradient_accum), _n.ptr(self.denom),
-                                                _n.ptr(self.max_radii2D), _n.current_stream_ptr(self.device))
-        if rc < 0:
-            raise RuntimeError("surfel_densify_stats failed: %s" % _n.last_error())
+        _n.call(self.device, "surfel_densify_stats", self.P, g, r, self.xyz_gradient_accum, self.denom, self.max_radii2D)
 
     def _rebuild(self, keep, new=None):
         """New store = rows `keep` (bool mask or None = all) of the old one, followed by the rows in `new`

@@ -6,10 +6,11 @@ already mapped by PyTorch-ROCm (same SONAME libamdhip64.so.7) is the one our lib
 here is plumbing only (device memory through its caching allocator, current stream).
 """
 import ctypes as C
+import math
 import os
 import threading
 
-import torch  # noqa: F401  (must precede the CDLL below, see module doc)
+import torch  # (must precede the CDLL below, see module doc)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SURFEL_LIB: diagnostics only (e.g. the -DSURFEL_IEEE_MATH twin built by `python build.py --ieee`)
@@ -18,46 +19,23 @@ LIB_PATH = os.environ.get("SURFEL_LIB") or os.path.join(_HERE, "lib", "libsurfel
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 HOOK_FN = C.CFUNCTYPE(None, C.c_void_p)
 
-EXPORTS = ["surfel_abi_version", "surfel_last_error", "surfel_rasterize_forward", "surfel_rasterize_backward",
-           "surfel_mark_visible", "surfel_knn_dist2", "surfel_last_stage_ms", "surfel_last_stage_ids", "surfel_stage_name",
-           "surfel_collect_stage_ms", "surfel_set_option", "surfel_debug_sort_pairs", "surfel_debug_set_blend_stats", "surfel_debug_last_binning", "surfel_debug_capacity_evictions", "surfel_debug_image_layout", "surfel_debug_box_probe", "surfel_debug_latency_probe", "surfel_set_backward_hook", "surfel_forward_count",
-           # include/surfel_train.h
-           "surfel_l1_ssim_forward", "surfel_l1_ssim_backward", "surfel_l1_ssim_forward_w", "surfel_l1_ssim_backward_w", "surfel_render_post_forward", "surfel_render_post_backward", "surfel_train_loss_forward", "surfel_train_loss_backward",
-           "surfel_reduce_partials", "surfel_loss_finalize", "surfel_activate", "surfel_adam_step", "surfel_train_update", "surfel_sh_grad_gather", "surfel_densify_stats"]
-# include/surfel_mesh.h
-MESH_EXPORTS = ["surfel_tsdf_table_bytes", "surfel_tsdf_block_bytes", "surfel_mesh_prepare_view", "surfel_tsdf_init", "surfel_tsdf_mark", "surfel_tsdf_allocate",
-                "surfel_tsdf_integrate", "surfel_tsdf_count", "surfel_tsdf_extract", "surfel_mesh_clusters", "surfel_mesh_filter"]
-# include/surfel_mesh_unbounded.h
-UNBOUNDED_EXPORTS = ["surfel_unbounded_bytes", "surfel_unbounded_init", "surfel_unbounded_fuse", "surfel_unbounded_count", "surfel_unbounded_extract",
-                     "surfel_unbounded_color"]
-# include/surfel_eval.h
-EVAL_EXPORTS = ["surfel_eval_sample_count", "surfel_eval_sample_emit", "surfel_eval_grid_build", "surfel_eval_thin", "surfel_eval_obs_mask",
-                "surfel_eval_above_plane", "surfel_eval_nearest", "surfel_eval_mean_below", "surfel_eval_dilate_masks", "surfel_eval_cull_vertices"]
 
-# per-call option overrides carried in the upper bits of the `debug` argument (include/surfel_hip.h)
-OPT_NO_CULL = 1 << 8
-OPT_BWD_QUAD = 1 << 11
-OPT_BWD_ROWS = 1 << 12
-OPT_PBWD_COOP = 1 << 13
-OPT_PBWD_THREAD = 1 << 14
-OPT_EXACT_BINNING = 1 << 16    # forward: size the binning buffers exactly (host wait for the instance count) for this call
-OPT_TILE_CUTS = 1 << 17        # backward: tile cuts instead of zero gradient records (default: R >= 2^21); bit-identical
-OPT_ZERO_RECORDS = 1 << 18     # backward: zero gradient records behind a tile's saturation point (default: R < 2^21)
-OPT_LAZY_COUNT = 1 << 21       # forward: do not wait for the instance count; forward_count() collects it (include/surfel_hip.h)
-E_OVERFLOW = -5
-OPT_BWD_GATHER = 1 << 22       # backward: ignore the forward's tile stream, gather by surfel id (bit-identical)
-OPT_NO_STREAM = 1 << 23        # forward: no backward follows (inference / no_grad): leave no tile stream behind
-OPT_PBWD_NO_JAC = 1 << 24      # backward: read the SH block again instead of the forward's d(colour)/d(direction) rows (same result to rounding)
-OPT_BWD_SCAN = 1 << 15         # scan walk (lanes = instances); deterministic, not bit-identical to rows / quad
+class DevPtr:
+    """Parameter type of a DEVICE pointer: a torch tensor passes as its data_ptr() and must live on a HIP device (a host address
+    must never reach a kernel), None as NULL, anything else (c_void_p, int, byref) as c_void_p takes it."""
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):
+            if not v.is_cuda:
+                raise RuntimeError("libsurfel_hip: tensors must live on a HIP device (got %s)" % v.device)
+            return C.c_void_p(v.data_ptr())
+        return None if v is None else C.c_void_p.from_param(v)
 
 
-def opt_tile_order(mode):
-    """per-call "tile_order" (0 auto, 1 XCD-contiguous, 2 longest lists first) in the debug word (SURFEL_OPT_TILE_ORDER)"""
-    return ((int(mode) + 1) & 3) << 19
-
-
-def opt_tile_sort(mode):
-    return ((mode + 1) & 3) << 9
+class Stream:
+    """Parameter type of `void* stream` (a hipStream_t), always the last parameter: call() fills it in."""
+    from_param = C.c_void_p.from_param
 
 
 class TsdfVolume(C.Structure):
@@ -86,6 +64,124 @@ class EvalGrid(C.Structure):
                 ("sorted", C.c_void_p), ("order", C.c_void_p), ("ranges", C.c_void_p)]
 
 
+# ---- every exported function: name -> (restype, parameter types ...), grouped by the header that declares it.  d = device pointer,
+# s = the stream, u = any other void*, a = allocator callback; host pointers keep their POINTER(...) type.
+_i, _i64, _f, _f64, _d, _s, _u, _a = C.c_int, C.c_int64, C.c_float, C.c_double, DevPtr, Stream, C.c_void_p, ALLOC_FN
+_fp, _ip, _i64p, _f64p = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+_vol, _uvol, _grid = C.POINTER(TsdfVolume), C.POINTER(UnboundedVolume), C.POINTER(EvalGrid)
+_adam = (_i, _d, _d, _d, _d, _d, _fp, _f, _f, _f, _i, _f, _i, _i, _d, _d)      # surfel_adam_step up to gcol_all
+SIGNATURES = {
+    "surfel_hip.h": {
+        "surfel_abi_version": (_i,),
+        "surfel_last_error": (C.c_char_p,),
+        "surfel_rasterize_forward": (_i64, _a, _u, _a, _u, _a, _u, _i, _i, _i, _d, _i, _i, _d, _d, _d, _d, _d, _f, _d, _d, _d, _d, _d, _f, _f, _i,
+                                     _d, _d, _d, _i, _s),
+        "surfel_rasterize_backward": (_i, _a, _u, _i, _i, _i, _i64, _d, _i, _i, _d, _d, _d, _d, _f, _d, _d, _d, _d, _d, _f, _f, _d, _d, _d, _d,
+                                      _d, _d, _d, _d, _d, _d, _d, _d, _d, _d, _d, _i, _s),
+        "surfel_mark_visible": (_i, _i, _d, _d, _d, _d, _s),
+        "surfel_knn_dist2": (_i, _a, _u, _i, _d, _d, _s),
+        "surfel_set_option": (_i, C.c_char_p, _i),
+        "surfel_set_backward_hook": (_i, HOOK_FN, _u),
+        "surfel_forward_count": (_i64,),
+    },
+    "surfel_debug.h": {
+        "surfel_last_stage_ms": (_i, _fp, _i),
+        "surfel_last_stage_ids": (_i, _ip, _i),
+        "surfel_collect_stage_ms": (_i, _fp, _ip, _i),
+        "surfel_stage_name": (C.c_char_p, _i),
+        "surfel_debug_sort_pairs": (_i, _a, _u, _d, _d, _i64, _i, _i, _s),
+        "surfel_debug_set_blend_stats": (_i, _d),
+        "surfel_debug_last_binning": (_i,),
+        "surfel_debug_capacity_evictions": (_i,),
+        "surfel_debug_image_layout": (_i, _i, _i, _i64p),
+        "surfel_debug_box_probe": (_i, _d, _i64, _fp, _s),
+        "surfel_debug_latency_probe": (_i, _d, _i64, _i, _fp, _s),
+    },
+    "surfel_train.h": {
+        "surfel_l1_ssim_forward": (_i, _i, _i, _i, _d, _d, _d, _d, _s),
+        "surfel_l1_ssim_backward": (_i, _i, _i, _i, _d, _d, _d, _f, _f, _d, _d, _d, _s),
+        "surfel_l1_ssim_forward_w": (_i, _i, _i, _i, _i, _d, _d, _d, _d, _s),
+        "surfel_l1_ssim_backward_w": (_i, _i, _i, _i, _i, _d, _d, _d, _f, _f, _d, _d, _d, _s),
+        "surfel_render_post_forward": (_i, _i, _i, _d, _d, _f, _d, _d, _s),
+        "surfel_render_post_backward": (_i, _i, _i, _d, _d, _f, _d, _f, _f, _d, _d, _s),
+        "surfel_train_loss_forward": (_i, _i, _i, _d, _d, _d, _d, _d, _d, _f, _d, _s),
+        "surfel_train_loss_backward": (_i, _i, _i, _d, _d, _d, _f, _f, _d, _d, _f, _f, _f, _d, _d, _d, _d, _d, _f, _f, _f, _d, _d, _s),
+        "surfel_reduce_partials": (_i, _d, _i, _i, _i, _f, _d, _s),
+        "surfel_loss_finalize": (_i, _d, _i, _i, _d, _i, _i, _f, _f, _f, _d, _d, _s),
+        "surfel_activate": (_i, _i, _d, _d, _s),
+        "surfel_adam_step": (_i,) + _adam + (_i, _s),
+        "surfel_train_update": (_i,) + _adam + (_d, _d, _d, _d, _d, _s),
+        "surfel_sh_grad_gather": (_i, _i, _i, _i, _d, _d, _d, _d, _s),
+        "surfel_densify_stats": (_i, _i, _d, _d, _d, _d, _d, _s),
+    },
+    "surfel_mesh.h": {
+        "surfel_tsdf_table_bytes": (_i64, _vol),
+        "surfel_tsdf_block_bytes": (_i64,),
+        "surfel_mesh_prepare_view": (_i, _i, _i, _d, _d, _d, _f, _d, _d, _s),
+        "surfel_tsdf_init": (_i, _vol, _a, _u, _s),
+        "surfel_tsdf_mark": (_i, _vol, _i, _i, _d, _d, _s),
+        "surfel_tsdf_allocate": (_i64, _vol, _a, _u, _s),
+        "surfel_tsdf_integrate": (_i, _vol, _i, _i, _d, _d, _d, _s),
+        "surfel_tsdf_count": (_i, _vol, _s),
+        "surfel_tsdf_extract": (_i, _vol, _d, _d, _d, _s),
+        "surfel_mesh_clusters": (_i, _a, _u, _i64, _i64, _d, _d, _d, _s),
+        "surfel_mesh_filter": (_i, _a, _u, _i64, _i64, _d, _d, _d, _d, _d, _i, _d, _d, _d, _i64p, _s),
+    },
+    "surfel_mesh_unbounded.h": {
+        "surfel_unbounded_bytes": (_i64, _uvol),
+        "surfel_unbounded_init": (_i, _uvol, _a, _u, _s),
+        "surfel_unbounded_fuse": (_i, _uvol, _i, _d, _d, _d, _s),
+        "surfel_unbounded_count": (_i, _uvol, _s),
+        "surfel_unbounded_extract": (_i, _uvol, _d, _d, _s),
+        "surfel_unbounded_color": (_i, _i64, _d, _i, _d, _d, _d, _f, _d, _s),
+    },
+    "surfel_eval.h": {
+        "surfel_eval_sample_count": (_i64, _a, _u, _i64, _i64, _d, _d, _f64, _i64, _d, _s),
+        "surfel_eval_sample_emit": (_i, _i64, _i64, _d, _d, _f64, _d, _i64, _d, _s),
+        "surfel_eval_grid_build": (_i, _a, _u, _grid, _i64, _d, _d, _s),
+        "surfel_eval_thin": (_i, _a, _u, _grid, _f, _d, _ip, _s),
+        "surfel_eval_obs_mask": (_i, _i64, _d, _fp, _f, _f64, _d, _ip, _d, _d, _s),
+        "surfel_eval_above_plane": (_i, _i64, _d, _f64p, _d, _s),
+        "surfel_eval_nearest": (_i, _a, _u, _grid, _i64, _d, _f, _d, _d, _s),
+        "surfel_eval_mean_below": (_i, _a, _u, _i64, _d, _f, _d, _s),
+        "surfel_eval_dilate_masks": (_i, _a, _u, _i, _i, _i, _d, _i, _d, _s),
+        "surfel_eval_cull_vertices": (_i, _i64, _d, _i, _d, _i, _i, _d, _d, _s),
+    },
+}
+EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
+MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
+UNBOUNDED_EXPORTS = list(SIGNATURES["surfel_mesh_unbounded.h"])
+EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])
+_SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
+
+
+# error codes and the per-call option overrides carried in the upper bits of the `debug` argument (include/surfel_hip.h, its order)
+E_LIMIT = -4
+E_OVERFLOW = -5
+OPT_NO_CULL = 1 << 8
+OPT_BWD_QUAD = 1 << 11
+OPT_BWD_ROWS = 1 << 12
+OPT_PBWD_COOP = 1 << 13
+OPT_PBWD_THREAD = 1 << 14
+OPT_BWD_SCAN = 1 << 15         # scan walk (lanes = instances); deterministic, not bit-identical to rows / quad
+OPT_EXACT_BINNING = 1 << 16    # forward: size the binning buffers exactly (host wait for the instance count) for this call
+OPT_TILE_CUTS = 1 << 17        # backward: tile cuts instead of zero gradient records (default: R >= 2^21); bit-identical
+OPT_ZERO_RECORDS = 1 << 18     # backward: zero gradient records behind a tile's saturation point (default: R < 2^21)
+OPT_LAZY_COUNT = 1 << 21       # forward: do not wait for the instance count; forward_count() collects it (include/surfel_hip.h)
+OPT_BWD_GATHER = 1 << 22       # backward: ignore the forward's tile stream, gather by surfel id (bit-identical)
+OPT_NO_STREAM = 1 << 23        # forward: no backward follows (inference / no_grad): leave no tile stream behind
+OPT_PBWD_NO_JAC = 1 << 24      # backward: read the SH block again instead of the forward's d(colour)/d(direction) rows (same result to rounding)
+
+
+def opt_tile_order(mode):
+    """per-call "tile_order" (0 auto, 1 XCD-contiguous, 2 longest lists first) in the debug word (SURFEL_OPT_TILE_ORDER)"""
+    return ((int(mode) + 1) & 3) << 19
+
+
+def opt_tile_sort(mode):
+    return ((mode + 1) & 3) << 9
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -102,102 +198,9 @@ def load():
                 "libsurfel_hip.so not found at %s — build it with `python 2d-gaussian-splatting_amd/build.py` "
                 "(hipcc --offload-arch=gfx950). There is no CPU / PyTorch fallback for the rasterizer." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        vp, f, i, i64 = C.c_void_p, C.c_float, C.c_int, C.c_int64
-        lib.surfel_abi_version.restype = i
-        lib.surfel_last_error.restype = C.c_char_p
-        lib.surfel_rasterize_forward.restype = i64
-        lib.surfel_rasterize_forward.argtypes = [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, i, i, i, vp, i, i,
-                                                 vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, i, vp, vp, vp, i, vp]
-        lib.surfel_rasterize_backward.restype = i
-        lib.surfel_rasterize_backward.argtypes = [ALLOC_FN, vp, i, i, i, i64, vp, i, i, vp, vp, vp, vp, f, vp, vp, vp, vp, vp,
-                                                  f, f, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
-        lib.surfel_mark_visible.restype = i
-        lib.surfel_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
-        lib.surfel_knn_dist2.restype = i
-        lib.surfel_knn_dist2.argtypes = [ALLOC_FN, vp, i, vp, vp, vp]
-        lib.surfel_last_stage_ms.restype = i
-        lib.surfel_last_stage_ms.argtypes = [C.POINTER(C.c_float), i]
-        lib.surfel_last_stage_ids.restype = i
-        lib.surfel_last_stage_ids.argtypes = [C.POINTER(C.c_int), i]
-        lib.surfel_collect_stage_ms.restype = i
-        lib.surfel_collect_stage_ms.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int), i]
-        lib.surfel_stage_name.restype = C.c_char_p
-        lib.surfel_stage_name.argtypes = [i]
-        lib.surfel_debug_sort_pairs.restype = i
-        lib.surfel_debug_sort_pairs.argtypes = [ALLOC_FN, vp, vp, vp, i64, i, i, vp]
-        lib.surfel_debug_set_blend_stats.restype = i
-        lib.surfel_debug_set_blend_stats.argtypes = [vp]
-        lib.surfel_debug_box_probe.restype = i
-        lib.surfel_debug_box_probe.argtypes = [vp, i64, C.POINTER(C.c_float), vp]
-        lib.surfel_debug_latency_probe.restype = i
-        lib.surfel_debug_latency_probe.argtypes = [vp, i64, i, C.POINTER(C.c_float), vp]
-        lib.surfel_set_backward_hook.restype = i
-        lib.surfel_set_backward_hook.argtypes = [HOOK_FN, vp]
-        lib.surfel_forward_count.restype = i64
-        lib.surfel_forward_count.argtypes = []
-        lib.surfel_set_option.restype = i
-        lib.surfel_set_option.argtypes = [C.c_char_p, i]
-        # ---- include/surfel_train.h
-        fp = C.POINTER(C.c_float)
-        for name, args in (("surfel_l1_ssim_forward", [i, i, i, vp, vp, vp, vp, vp]),
-                           ("surfel_l1_ssim_backward", [i, i, i, vp, vp, vp, f, f, vp, vp, vp, vp]),
-                           ("surfel_l1_ssim_forward_w", [i, i, i, i, vp, vp, vp, vp, vp]),
-                           ("surfel_l1_ssim_backward_w", [i, i, i, i, vp, vp, vp, f, f, vp, vp, vp, vp]),
-                           ("surfel_render_post_forward", [i, i, vp, vp, f, vp, vp, vp]),
-                           ("surfel_render_post_backward", [i, i, vp, vp, f, vp, f, f, vp, vp, vp]),
-                           ("surfel_train_loss_forward", [i, i, vp, vp, vp, vp, vp, vp, f, vp, vp]),
-                           ("surfel_train_loss_backward", [i, i, vp, vp, vp, f, f, vp, vp, f, f, f, vp, vp, vp, vp, vp, f, f, f, vp, vp, vp]),
-                           ("surfel_reduce_partials", [vp, i, i, i, f, vp, vp]),
-                           ("surfel_loss_finalize", [vp, i, i, vp, i, i, f, f, f, vp, vp, vp]),
-                           ("surfel_activate", [i, vp, vp, vp]),
-                           ("surfel_adam_step", [i, vp, vp, vp, vp, vp, fp, f, f, f, i, f, i, i, vp, vp, i, vp]),
-                           ("surfel_train_update", [i, vp, vp, vp, vp, vp, fp, f, f, f, i, f, i, i, vp, vp, vp, vp, vp, vp, vp, vp]),
-                           ("surfel_sh_grad_gather", [i, i, i, vp, vp, vp, vp, vp]),
-                           ("surfel_densify_stats", [i, vp, vp, vp, vp, vp, vp])):
+        for name, (restype, *argtypes) in _SIG.items():
             fn = getattr(lib, name)
-            fn.restype = i
-            fn.argtypes = args
-        # ---- include/surfel_mesh.h
-        vol = C.POINTER(TsdfVolume)
-        for name, res, args in (("surfel_tsdf_table_bytes", i64, [vol]), ("surfel_tsdf_block_bytes", i64, []),
-                                ("surfel_mesh_prepare_view", i, [i, i, vp, vp, vp, f, vp, vp, vp]),
-                                ("surfel_tsdf_init", i, [vol, ALLOC_FN, vp, vp]),
-                                ("surfel_tsdf_mark", i, [vol, i, i, vp, vp, vp]),
-                                ("surfel_tsdf_allocate", i64, [vol, ALLOC_FN, vp, vp]),
-                                ("surfel_tsdf_integrate", i, [vol, i, i, vp, vp, vp, vp]),
-                                ("surfel_tsdf_count", i, [vol, vp]),
-                                ("surfel_tsdf_extract", i, [vol, vp, vp, vp, vp]),
-                                ("surfel_mesh_clusters", i, [ALLOC_FN, vp, i64, i64, vp, vp, vp, vp]),
-                                ("surfel_mesh_filter", i, [ALLOC_FN, vp, i64, i64, vp, vp, vp, vp, vp, i, vp, vp, vp, C.POINTER(C.c_int64), vp])):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        # ---- include/surfel_mesh_unbounded.h
-        uvol = C.POINTER(UnboundedVolume)
-        for name, res, args in (("surfel_unbounded_bytes", i64, [uvol]),
-                                ("surfel_unbounded_init", i, [uvol, ALLOC_FN, vp, vp]),
-                                ("surfel_unbounded_fuse", i, [uvol, i, vp, vp, vp, vp]),
-                                ("surfel_unbounded_count", i, [uvol, vp]),
-                                ("surfel_unbounded_extract", i, [uvol, vp, vp, vp]),
-                                ("surfel_unbounded_color", i, [i64, vp, i, vp, vp, vp, f, vp, vp])):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        # ---- include/surfel_eval.h
-        eg, d = C.POINTER(EvalGrid), C.c_double
-        for name, res, args in (("surfel_eval_sample_count", i64, [ALLOC_FN, vp, i64, i64, vp, vp, d, i64, vp, vp]),
-                                ("surfel_eval_sample_emit", i, [i64, i64, vp, vp, d, vp, i64, vp, vp]),
-                                ("surfel_eval_grid_build", i, [ALLOC_FN, vp, eg, i64, vp, vp, vp]),
-                                ("surfel_eval_thin", i, [ALLOC_FN, vp, eg, f, vp, C.POINTER(i), vp]),
-                                ("surfel_eval_obs_mask", i, [i64, vp, C.POINTER(f), f, d, vp, C.POINTER(i), vp, vp, vp]),
-                                ("surfel_eval_above_plane", i, [i64, vp, C.POINTER(d), vp, vp]),
-                                ("surfel_eval_nearest", i, [ALLOC_FN, vp, eg, i64, vp, f, vp, vp, vp]),
-                                ("surfel_eval_mean_below", i, [ALLOC_FN, vp, i64, vp, f, vp, vp]),
-                                ("surfel_eval_dilate_masks", i, [ALLOC_FN, vp, i, i, i, vp, i, vp, vp]),
-                                ("surfel_eval_cull_vertices", i, [i64, vp, i, vp, i, i, vp, vp, vp])):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.surfel_abi_version() != 1:
             raise ImportError("libsurfel_hip.so ABI version mismatch")
         # SURFEL_OPTIONS="name=value,..." -> surfel_set_option (A/B runs of an unmodified caller, e.g. bench.py)
@@ -209,6 +212,40 @@ def load():
     return _lib
 
 
+class LimitError(RuntimeError):
+    """SURFEL_E_LIMIT: a size exceeds an internal limit or the caller's byte budget (raise the budget or coarsen the input)."""
+
+
+class CapacityOverflow(RuntimeError):
+    """a lazily counted frame held more tile instances than its capacity: render it again (OPT_EXACT_BINNING)"""
+
+
+_ERRORS = {E_LIMIT: LimitError, E_OVERFLOW: CapacityOverflow}
+_STREAMED = frozenset(name for name, sig in _SIG.items() if sig[-1] is Stream)
+
+
+def call(device, name, *args):
+    """The one path from Python into the library: `name`(*args) with `device` current and, where the function's last parameter is
+    the stream, that device's current stream appended.  device=None: a call that touches no device (no device guard, a NULL
+    stream).  Tensors pass as they are (DevPtr).  Returns the return code when it is >= 0; a negative one raises LimitError
+    (SURFEL_E_LIMIT), CapacityOverflow (SURFEL_E_OVERFLOW) or RuntimeError, each with the code and the library's message.  The
+    function is looked up on the loaded library at every call, so a proxy put in its place (scripts/host_split.py) sees them all."""
+    fn = getattr(load(), name)
+    if name in _STREAMED:
+        args += (None if device is None else current_stream_ptr(device),)
+    try:
+        if device is None:
+            rc = fn(*args)
+        else:
+            with torch.cuda.device(device):
+                rc = fn(*args)
+    except C.ArgumentError as e:      # ctypes' wrapper around what a parameter type refused (DevPtr: a host tensor)
+        raise RuntimeError("%s: %s" % (name, e)) from None
+    if rc < 0:
+        raise _ERRORS.get(rc, RuntimeError)("%s failed (%d): %s" % (name, rc, last_error()))
+    return rc
+
+
 _hook_keepalive = None
 
 
@@ -216,29 +253,15 @@ def set_backward_hook(fn):
     """surfel_set_backward_hook: fn() is called inside every rasterizer backward once dL/dcolour is final on the stream (None
     removes the hook).  The ctypes thunk is kept alive here for as long as the hook is installed."""
     global _hook_keepalive
-    lib = load()
-    if fn is None:
-        lib.surfel_set_backward_hook(HOOK_FN(), None)
-        _hook_keepalive = None
-        return
-    thunk = HOOK_FN(lambda user: fn())
-    lib.surfel_set_backward_hook(thunk, None)
-    _hook_keepalive = thunk
-
-
-class CapacityOverflow(RuntimeError):
-    """a lazily counted frame held more tile instances than its capacity: render it again (OPT_EXACT_BINNING)"""
+    thunk = HOOK_FN() if fn is None else HOOK_FN(lambda user: fn())
+    call(None, "surfel_set_backward_hook", thunk, None)
+    _hook_keepalive = None if fn is None else thunk
 
 
 def forward_count():
     """surfel_forward_count: exact instance count of this thread's last forward; raises CapacityOverflow for a lazily counted frame
     whose lists were truncated."""
-    r = load().surfel_forward_count()
-    if r == E_OVERFLOW:
-        raise CapacityOverflow(last_error())
-    if r < 0:
-        raise RuntimeError("surfel_forward_count failed: %s" % last_error())
-    return int(r)
+    return int(call(None, "surfel_forward_count"))
 
 
 def last_error():
@@ -282,6 +305,13 @@ class TorchAllocator:
 
     def last(self):
         return self.held[-1]
+
+    def view(self, pointer, dtype, shape):
+        """The held buffer that starts at `pointer` (an address the library reported), viewed as `shape` elements of `dtype`."""
+        for t in self.held:
+            if t.data_ptr() == pointer:
+                return t[:math.prod(shape) * dtype.itemsize].view(dtype).view(*shape)
+        raise KeyError(pointer)
 
 
 def ptr(t):

@@ -17,12 +17,6 @@ from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRas
 _n.load()
 
 
-def _check(rc, what):
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, _n.last_error()))
-    return rc
-
-
 # ------------------------------------------------------------------------------------------------ camera
 def world2view(R, t, translate=(0.0, 0.0, 0.0), scale=1.0):
     """W2C 4x4 from the C2W rotation R and the W2C translation t, with the reference's optional scene
@@ -128,9 +122,7 @@ class _RenderPost(torch.autograd.Function):
         am = allmap.detach().contiguous().float()
         H, W = int(am.shape[1]), int(am.shape[2])
         maps = torch.empty((9, H, W), dtype=torch.float32, device=am.device)
-        with torch.cuda.device(am.device):
-            _check(_n.load().surfel_render_post_forward(H, W, _n.ptr(am), _n.ptr(cam), float(depth_ratio), _n.ptr(maps), None,
-                                                        _n.current_stream_ptr(am.device)), "surfel_render_post_forward")
+        _n.call(am.device, "surfel_render_post_forward", H, W, am, cam, float(depth_ratio), maps, None)
         ctx.save_for_backward(am, cam)
         ctx.ratio = float(depth_ratio)
         return maps
@@ -141,9 +133,7 @@ class _RenderPost(torch.autograd.Function):
         H, W = int(am.shape[1]), int(am.shape[2])
         g = g_maps.contiguous().float()
         out = torch.empty_like(am)
-        with torch.cuda.device(am.device):
-            _check(_n.load().surfel_render_post_backward(H, W, _n.ptr(am), _n.ptr(cam), ctx.ratio, _n.ptr(g), 0.0, 0.0, None, _n.ptr(out),
-                                                         _n.current_stream_ptr(am.device)), "surfel_render_post_backward")
+        _n.call(am.device, "surfel_render_post_backward", H, W, am, cam, ctx.ratio, g, 0.0, 0.0, None, out)
         return out, None, None
 
 
@@ -160,16 +150,12 @@ class _Regularizers(torch.autograd.Function):
         am = allmap.detach().contiguous().float()
         dev = am.device
         H, W = int(am.shape[1]), int(am.shape[2])
-        lib = _n.load()
         nblk = ((W + 15) // 16) * ((H + 15) // 16)
         maps = torch.empty((9, H, W), dtype=torch.float32, device=dev)
         partials = torch.empty((nblk, 2), dtype=torch.float32, device=dev)
         means = torch.empty((2,), dtype=torch.float32, device=dev)
-        s = _n.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            _check(lib.surfel_render_post_forward(H, W, _n.ptr(am), _n.ptr(cam), float(depth_ratio), _n.ptr(maps), _n.ptr(partials), s),
-                   "surfel_render_post_forward")
-            _check(lib.surfel_reduce_partials(_n.ptr(partials), 1, nblk, 2, 1.0 / (H * W), _n.ptr(means), s), "surfel_reduce_partials")
+        _n.call(dev, "surfel_render_post_forward", H, W, am, cam, float(depth_ratio), maps, partials)
+        _n.call(dev, "surfel_reduce_partials", partials, 1, nblk, 2, 1.0 / (H * W), means)
         ctx.save_for_backward(am, cam)
         ctx.k = (float(depth_ratio), float(lambda_normal), float(lambda_dist))
         ctx.mark_non_differentiable(means)
@@ -182,9 +168,7 @@ class _Regularizers(torch.autograd.Function):
         H, W = int(am.shape[1]), int(am.shape[2])
         g = g_loss.contiguous().float().reshape(1)
         out = torch.empty_like(am)
-        with torch.cuda.device(am.device):
-            _check(_n.load().surfel_render_post_backward(H, W, _n.ptr(am), _n.ptr(cam), ratio, None, ln / (H * W), ld / (H * W), _n.ptr(g),
-                                                         _n.ptr(out), _n.current_stream_ptr(am.device)), "surfel_render_post_backward")
+        _n.call(am.device, "surfel_render_post_backward", H, W, am, cam, ratio, None, ln / (H * W), ld / (H * W), g, out)
         return out, None, None, None, None
 
 

@@ -158,7 +158,6 @@ def test_image_layout_mirror_matches_the_library():
     import surfel_native
     import diff_surfel_rasterization as dsr
     lib = surfel_native.load()
-    lib.surfel_debug_image_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     out = (ctypes.c_int64 * 6)()
     for W, H in [(1, 1), (16, 16), (72, 56), (800, 800), (800, 600), (1600, 1060), (1920, 1080), (3840, 2160), (1023, 1025)]:
         assert lib.surfel_debug_image_layout(W, H, out) == 0
@@ -167,3 +166,104 @@ def test_image_layout_mirror_matches_the_library():
         tiles = gx * gy
         assert tile_map < out[0] < tile_map + 4 * 32 * (tiles // 8 + 64) + 256
     assert lib.surfel_debug_image_layout(0, 4, out) < 0
+
+
+HEADERS = ("surfel_hip.h", "surfel_debug.h", "surfel_train.h", "surfel_mesh.h", "surfel_mesh_unbounded.h", "surfel_eval.h")
+
+
+def _prototypes(hdr):
+    """[(name, return type, [(parameter type, parameter name)])] of every function a header declares (comments stripped; the headers
+    are plain C), and the number of `surfel_xxx(` occurrences outside comments and typedefs, which must be the same number."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", hdr)).read(), flags=re.S)
+    src = re.sub(r"^\s*(#|typedef\s[^{;]*;).*$", "", src, flags=re.M)
+    protos = []
+    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(surfel_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        plist = []
+        for p in (x.strip() for x in params.split(",")):
+            if p != "void":
+                m = re.fullmatch(r"(.*?)(\w+)", p, flags=re.S)
+                plist.append((re.sub(r"\bconst\b|\s+", "", m.group(1)), m.group(2)))
+        protos.append((name, re.sub(r"\s+", "", ret), plist))
+    return protos, len(re.findall(r"\bsurfel_[a-z0-9_]+\s*\(", src))
+
+
+def test_every_signature_matches_its_header():
+    """surfel_native.SIGNATURES against all six headers: return type, arity and the kind of every parameter of every function.  No
+    function is skipped: a header that gains, loses or retypes a parameter fails here."""
+    import ctypes as C
+    import surfel_native as n
+    lib = n.load()
+    scalars = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "surfel_alloc_fn": n.ALLOC_FN,
+               "surfel_hook_fn": n.HOOK_FN}
+    structs = {"surfel_tsdf_volume*": n.TsdfVolume, "surfel_unbounded_volume*": n.UnboundedVolume, "surfel_eval_grid*": n.EvalGrid}
+    returns = {"int": C.c_int, "int64_t": C.c_int64, "constchar*": C.c_char_p}
+    parsed = checked = 0
+    for hdr in HEADERS:
+        protos, mentions = _prototypes(hdr)
+        assert len(protos) == mentions, (hdr, len(protos), mentions)
+        assert sorted(p[0] for p in protos) == sorted(n.SIGNATURES[hdr]), hdr
+        parsed += len(protos)
+        for name, ret, params in protos:
+            fn = getattr(lib, name)
+            assert fn.restype is returns[ret], (name, ret, fn.restype)
+            assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, fn.argtypes, params)
+            for k, ((ctype, pname), at) in enumerate(zip(params, fn.argtypes)):
+                where = (name, k, ctype, pname, at)
+                if ctype in scalars:
+                    assert at is scalars[ctype], where
+                elif ctype in structs:
+                    assert at is C.POINTER(structs[ctype]), where
+                elif ctype == "char*":
+                    assert at is C.c_char_p, where
+                else:
+                    assert ctype.endswith("*"), where
+                    assert at in (n.DevPtr, n.Stream, C.c_void_p) or issubclass(at, C._Pointer), where
+                # the stream is the last parameter, and call() appends it exactly there
+                assert (at is n.Stream) == (pname == "stream") and (pname != "stream" or k == len(params) - 1), where
+            checked += 1
+    assert checked == parsed and parsed >= 62
+    assert parsed == len(n.EXPORTS + n.MESH_EXPORTS + n.UNBOUNDED_EXPORTS + n.EVAL_EXPORTS)
+
+
+def test_call_maps_error_codes_without_a_device():
+    """surfel_native.call: a negative return code raises with the code and the library's own message; SURFEL_E_LIMIT is LimitError (the
+    one class the mesh and evaluation modules export as MeshLimitError).  All four calls fail before the library touches a device."""
+    import ctypes as C
+    import torch
+    import surfel_eval
+    import surfel_mesh
+    import surfel_native as n
+    assert surfel_mesh.MeshLimitError is surfel_eval.MeshLimitError is n.LimitError and issubclass(n.LimitError, RuntimeError)
+    out = (C.c_int64 * 4)()
+    assert n.call(None, "surfel_debug_image_layout", 16, 16, out) == 0
+    with pytest.raises(RuntimeError, match=r"\(-1\): .*bad arguments") as e:
+        n.call(None, "surfel_debug_image_layout", 0, 4, out)
+    assert not isinstance(e.value, (n.LimitError, n.CapacityOverflow))
+    with pytest.raises(RuntimeError, match=r"surfel_set_option failed \(-1\): .*unknown option"):
+        n.call(None, "surfel_set_option", b"no_such_option", 1)
+    v = n.TsdfVolume()
+    v.dims[:] = [1, 1, 1]
+    v.voxel_size, v.sdf_trunc, v.budget_bytes = 0.01, 0.05, 0
+    taken = []
+    cb = n.ALLOC_FN(lambda user, nbytes: taken.append(nbytes) or None)
+    with pytest.raises(n.LimitError, match=r"\(-4\): .*budget"):
+        n.call(None, "surfel_tsdf_init", v, cb, None)
+    with pytest.raises(n.LimitError, match=r"\(-4\): .*budget"):
+        n.call(None, "surfel_eval_sample_count", cb, None, 1000, 0, C.c_void_p(256), None, 0.2, 11999, None)
+    assert not taken
+    # a host tensor never reaches a device-pointer parameter
+    with pytest.raises(RuntimeError, match="HIP device"):
+        n.call(None, "surfel_debug_set_blend_stats", torch.zeros(8, dtype=torch.int64))
+    with pytest.raises(C.ArgumentError, match="HIP device"):      # the same refusal for a caller that goes to the library directly
+        n.load().surfel_activate(1, torch.zeros(58), torch.zeros(7), None)
+
+
+def test_allocator_view_finds_a_held_buffer_by_its_address():
+    import torch
+    import surfel_native as n
+    a = n.TorchAllocator("cpu")
+    p0, p1 = a.cb(None, 64), a.cb(None, 4096)
+    v = a.view(p1, torch.float32, (4, 8))
+    assert v.shape == (4, 8) and v.dtype == torch.float32 and v.data_ptr() == p1 and a.view(p0, torch.uint8, (64,)).data_ptr() == p0
+    with pytest.raises(KeyError):
+        a.view(p1 + 4, torch.float32, (1,))
