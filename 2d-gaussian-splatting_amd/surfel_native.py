@@ -147,11 +147,20 @@ SIGNATURES = {
         "surfel_eval_dilate_masks": (_i, _a, _u, _i, _i, _i, _d, _i, _d, _s),
         "surfel_eval_cull_vertices": (_i, _i64, _d, _i, _d, _i, _i, _d, _d, _s),
     },
+    "surfel_eval_tnt.h": {
+        "surfel_tnt_mesh_cloud": (_i, _i64, _i64, _d, _d, _d, _s),
+        "surfel_tnt_transform": (_i, _i64, _d, _f64p, _d, _s),
+        "surfel_tnt_crop": (_i, _i64, _d, _i, _f64, _f64, _i, _d, _d, _s),
+        "surfel_tnt_voxel_down_sample": (_i64, _a, _u, _i64, _d, _f64, _f64p, _i64, _d, _d, _d, _s),
+        "surfel_tnt_corr_sums": (_i, _a, _u, _i64, _d, _d, _i64, _d, _d, _s),
+        "surfel_tnt_histogram": (_i, _i64, _d, _i, _d, _f64, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
 UNBOUNDED_EXPORTS = list(SIGNATURES["surfel_mesh_unbounded.h"])
 EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])
+TNT_EXPORTS = list(SIGNATURES["surfel_eval_tnt.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 
