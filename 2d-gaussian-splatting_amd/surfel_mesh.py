@@ -346,6 +346,21 @@ class GaussianExtractor:
         self.lattice = lat
         return TriangleMesh(verts, tris, cols)
 
+    @torch.no_grad()
+    def export_image(self, path):
+        """utils/mesh_utils.py:282-292 without vis/: path/renders/%05d.png from rgbmaps and path/gt/%05d.png from original_image[0:3],
+        quantised as save_img_u8 does (render_utils.py:270-275): NaN -> 0, clip to [0, 1], times 255, truncated to uint8.  What
+        surfel_metrics.evaluate reads (METRICS.md)."""
+        from PIL import Image
+        render_path, gts_path = os.path.join(path, "renders"), os.path.join(path, "gt")
+        os.makedirs(render_path, exist_ok=True)
+        os.makedirs(gts_path, exist_ok=True)
+        for idx, cam in enumerate(self.viewpoint_stack):
+            for img, folder in ((cam.original_image[0:3], gts_path), (self.rgbmaps[idx], render_path)):
+                a = img.detach().permute(1, 2, 0).cpu().numpy()
+                u8 = (np.clip(np.nan_to_num(a), 0.0, 1.0) * 255.0).astype(np.uint8)
+                Image.fromarray(u8).save(os.path.join(folder, "%05d.png" % idx), "PNG")
+
 
 def cluster_triangles(mesh):
     """(label [F] = smallest triangle id of the triangle's edge-connected cluster, size [F] = triangles per label id)."""

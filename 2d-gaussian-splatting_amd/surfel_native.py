@@ -155,12 +155,21 @@ SIGNATURES = {
         "surfel_tnt_corr_sums": (_i, _a, _u, _i64, _d, _d, _i64, _d, _d, _s),
         "surfel_tnt_histogram": (_i, _i64, _d, _i, _d, _f64, _d, _s),
     },
+    "surfel_metrics.h": {
+        "surfel_lpips_workspace_bytes": (_i64, _i, _i, _i64),
+        "surfel_lpips_prepare": (_i, _i, _i, _d, _d, _d, _s),
+        "surfel_lpips_conv3x3": (_i, _i, _i, _i, _i, _d, _d, _d, _d, _s),
+        "surfel_lpips_pool": (_i, _i, _i, _i, _d, _d, _s),
+        "surfel_lpips_tap": (_i, _i, _i, _i, _d, _d, _d, _s),
+        "surfel_sq_err_partials": (_i, _i64, _d, _d, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
 UNBOUNDED_EXPORTS = list(SIGNATURES["surfel_mesh_unbounded.h"])
 EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])
 TNT_EXPORTS = list(SIGNATURES["surfel_eval_tnt.h"])
+METRICS_EXPORTS = list(SIGNATURES["surfel_metrics.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 
