@@ -20,6 +20,22 @@ def write_ply(path, names, columns):
         f.write(columns.tobytes())
 
 
+def write_ply_records(path, rec):
+    """rec: 1-D structured array of scalar little-endian fields -> binary_little_endian PLY with one `vertex` property per field, each of
+    its own type (e.g. the float x y z nx ny nz + uchar red green blue of the reference's points3D.ply)."""
+    names = {"i1": "char", "u1": "uchar", "i2": "short", "u2": "ushort", "i4": "int", "u4": "uint", "f4": "float", "f8": "double"}
+    rec = np.ascontiguousarray(rec)
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % rec.shape[0]]
+    for n in rec.dtype.names:
+        t = rec.dtype[n]
+        if t.shape or t.byteorder == ">" or t.str[1:] not in names:
+            raise ValueError("field %s: unsupported type %s" % (n, t))
+        header.append("property %s %s" % (names[t.str[1:]], n))
+    with open(path, "wb") as f:
+        f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
 def read_ply(path):
     """Returns {property name: 1-D numpy array} of the first element (`vertex`).  Handles binary little/big endian and
     ascii; list properties are not supported (the reference's point clouds have none)."""

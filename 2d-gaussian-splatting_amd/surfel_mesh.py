@@ -405,6 +405,21 @@ def _latest_iteration(model_dir):
     return max(its)
 
 
+def _scene_cameras(args, gaussians, it):
+    """(train, test) cameras of the capture at args.source_path, loaded the way the training run loaded them: images folder, resolution,
+    split and background from model_path/cfg_args (surfel_trainer.write_cfg_args) where it exists."""
+    from surfel_scene import Scene
+    cfg = argparse.Namespace(images="images", resolution=-1, eval=False, white_background=False)
+    path = os.path.join(args.model_path, "cfg_args")
+    if os.path.exists(path):
+        cfg = eval(open(path).read(), {"Namespace": argparse.Namespace, "__builtins__": {}})
+    args.white_background = args.white_background or getattr(cfg, "white_background", False)      # renders over what the images were composited on
+    scene = Scene(args.source_path, args.model_path, images=getattr(cfg, "images", "images"), resolution=getattr(cfg, "resolution", -1),
+                  white_background=args.white_background, eval=getattr(cfg, "eval", False),
+                  data_device=str(gaussians.device), load_iteration=it, shuffle=False, gaussians=gaussians)
+    return scene.getTrainCameras(), scene.getTestCameras()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="TSDF mesh of a trained model (render.py's mesh step), bounded or --unbounded. Unlike the reference, which "
                                              "fuses only the training split, every camera in cameras.json is fused.")
@@ -419,6 +434,8 @@ def main(argv=None):
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--unbounded", action="store_true", help="Mesh: unbounded mode (contracted lattice of mesh_res, a multiple of 512)")
     ap.add_argument("--budget_gb", default=DEFAULT_BUDGET / 2 ** 30, type=float, help="byte budget of the TSDF volume (GiB)")
+    ap.add_argument("-s", "--source_path", default=None, help="the capture the model was trained on: cameras and ground-truth images come from it "
+                    "(surfel_scene.Scene, with the model's cfg_args), only the training split is fused, and renders / gt of both splits are exported")
     args = ap.parse_args(argv)
     import surfel_io
     import surfel_model
@@ -426,13 +443,22 @@ def main(argv=None):
     dev = torch.device("cuda")
     it = _latest_iteration(args.model_path) if args.iteration < 0 else args.iteration
     gaussians = surfel_model.GaussianModel(3, device=dev)
-    gaussians.load_ply(os.path.join(args.model_path, "point_cloud", "iteration_%d" % it, "point_cloud.ply"))
-    cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=dev)
+    test_cams = []
+    if args.source_path is None:
+        gaussians.load_ply(os.path.join(args.model_path, "point_cloud", "iteration_%d" % it, "point_cloud.ply"))
+        cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=dev)
+    else:
+        cams, test_cams = _scene_cameras(args, gaussians, it)      # (loads the point cloud of iteration `it` into gaussians)
     pipe = argparse.Namespace(depth_ratio=args.depth_ratio, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
     ext = GaussianExtractor(gaussians, render, pipe, bg_color=[1, 1, 1] if args.white_background else [0, 0, 0])
     ext.budget_bytes = int(args.budget_gb * 2 ** 30)
     out = os.path.join(args.model_path, "train", "ours_%d" % it)
     os.makedirs(out, exist_ok=True)
+    if args.source_path is not None:      # render.py:68-84: renders (at the trained SH degree) / gt of both splits, where surfel_metrics.py looks for them
+        for split, split_cams in (("train", cams), ("test", test_cams)):
+            if split_cams:
+                ext.reconstruction(split_cams)
+                ext.export_image(os.path.join(args.model_path, split, "ours_%d" % it))
     gaussians.active_sh_degree = 0      # render.py:91: diffuse colour only
     ext.reconstruction(cams)
     if args.unbounded:

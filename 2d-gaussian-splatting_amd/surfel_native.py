@@ -163,6 +163,13 @@ SIGNATURES = {
         "surfel_lpips_tap": (_i, _i, _i, _i, _d, _d, _d, _s),
         "surfel_sq_err_partials": (_i, _i64, _d, _d, _d, _s),
     },
+    "surfel_scene.h": {
+        "surfel_scene_resample_table": (_i, _i, _i, _ip, _ip, _i64),
+        "surfel_scene_resample_h": (_i, _i, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _s),
+        "surfel_scene_resample_v": (_i, _i, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _s),
+        "surfel_scene_to_float": (_i, _i, _i, _i, _d, _d, _d, _s),
+        "surfel_scene_composite": (_i, _i, _i, _i, _d, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -170,6 +177,7 @@ UNBOUNDED_EXPORTS = list(SIGNATURES["surfel_mesh_unbounded.h"])
 EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])
 TNT_EXPORTS = list(SIGNATURES["surfel_eval_tnt.h"])
 METRICS_EXPORTS = list(SIGNATURES["surfel_metrics.h"])
+SCENE_EXPORTS = list(SIGNATURES["surfel_scene.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

@@ -585,3 +585,109 @@ def training(model, cams, opt=None, pipe=None, iterations=None, white_background
             dt = time.perf_counter() - t0
             print("[it %d] loss %.5f points %d  %.1f it/s" % (tr.iteration, float(tr.last["loss"]), model.P, tr.iteration / dt), flush=True)
     return tr
+
+
+# ------------------------------------------------------------------------------------------------ CLI (train.py:31-144, 146-160, 251-278)
+_MODEL_ARGS = ("sh_degree", "source_path", "model_path", "images", "resolution", "white_background", "data_device", "eval")
+_OPTIMIZATION_ARGS = ("iterations", "position_lr_init", "position_lr_final", "position_lr_delay_mult", "position_lr_max_steps", "feature_lr",
+                      "opacity_lr", "scaling_lr", "rotation_lr", "percent_dense", "lambda_dssim", "lambda_dist", "lambda_normal", "opacity_cull",
+                      "densification_interval", "opacity_reset_interval", "densify_from_iter", "densify_until_iter", "densify_grad_threshold")
+
+
+def parse_args(argv=None):
+    """The reference's flags with its defaults (arguments/__init__.py:47-95, train.py:258-265), without the viewer's --ip / --port."""
+    import argparse
+    import os
+    ap = argparse.ArgumentParser(description="Train a 2-D Gaussian surfel model on a COLMAP or Blender capture")
+    g = ap.add_argument_group("Loading Parameters")
+    g.add_argument("--source_path", "-s", default="", type=str)
+    g.add_argument("--model_path", "-m", default="", type=str)
+    g.add_argument("--images", "-i", default="images", type=str)
+    g.add_argument("--resolution", "-r", default=-1, type=int)
+    g.add_argument("--white_background", "-w", default=False, action="store_true")
+    g.add_argument("--sh_degree", default=3, type=int)
+    g.add_argument("--data_device", default="cuda", type=str)
+    g.add_argument("--eval", default=False, action="store_true")
+    g = ap.add_argument_group("Optimization Parameters")
+    defaults = vars(optimization_params())
+    for name in _OPTIMIZATION_ARGS:
+        g.add_argument("--" + name, default=defaults[name], type=type(defaults[name]))
+    g = ap.add_argument_group("Pipeline Parameters")
+    g.add_argument("--depth_ratio", default=0.0, type=float)
+    ap.add_argument("--test_iterations", nargs="+", type=int, default=[7_000, 30_000])
+    ap.add_argument("--save_iterations", nargs="+", type=int, default=[7_000, 30_000])
+    ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[])
+    ap.add_argument("--start_checkpoint", type=str, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--workers", type=int, default=4, help="image decoding threads (at most 8)")
+    args = ap.parse_args(argv)
+    args.save_iterations = list(args.save_iterations) + [args.iterations]
+    args.source_path = os.path.abspath(args.source_path)
+    return args
+
+
+def optimization_from_args(args):
+    return optimization_params(**{name: getattr(args, name) for name in _OPTIMIZATION_ARGS})
+
+
+def write_cfg_args(args):
+    """model_path/cfg_args = str(Namespace(...)) of the loading parameters (train.py:146-160), which the reference's render.py and
+    metrics.py evaluate back (arguments/__init__.py:97-117)."""
+    import argparse
+    import os
+    os.makedirs(args.model_path, exist_ok=True)
+    path = os.path.join(args.model_path, "cfg_args")
+    with open(path, "w") as f:
+        f.write(str(argparse.Namespace(**{k: getattr(args, k) for k in _MODEL_ARGS})))
+    return path
+
+
+def main(argv=None):
+    """python surfel_trainer.py -s <capture> -m <model folder> [...]: trains, saves point_cloud/iteration_N at the save iterations (the
+    last iteration always among them), checkpoints as (capture(), iteration), and reports L1 / PSNR of the test split and of a train
+    subset at the test iterations."""
+    import os
+    import uuid
+    from surfel_scene import Scene
+    args = parse_args(argv)
+    if not args.model_path:
+        args.model_path = os.path.join("./output/", str(uuid.uuid4())[0:10])
+    say = (lambda *a, **k: None) if args.quiet else print
+    say("Optimizing " + args.model_path)
+    random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
+    write_cfg_args(args)
+    opt, pipe = optimization_from_args(args), pipeline_params(depth_ratio=args.depth_ratio)
+    scene = Scene(args.source_path, args.model_path, images=args.images, resolution=args.resolution, white_background=args.white_background,
+                  eval=args.eval, data_device=args.data_device, seed=args.seed, workers=args.workers, sh_degree=args.sh_degree)
+    model, first_iter = scene.gaussians, 0
+    model.training_setup(opt)
+    if args.start_checkpoint:
+        model_params, first_iter = torch.load(args.start_checkpoint, weights_only=False)
+        model.restore(model_params, opt)
+    tr = Trainer(model, scene.getTrainCameras(), opt, pipe, args.white_background, extent=scene.cameras_extent, seed=args.seed, first_iter=first_iter)
+    train_cams = scene.getTrainCameras()
+    reports = (("test", scene.getTestCameras()), ("train", [train_cams[i % len(train_cams)] for i in range(5, 30, 5)]))
+    t0 = time.perf_counter()
+    while tr.iteration < opt.iterations:
+        tr.step()
+        it = tr.iteration
+        if it in args.test_iterations:
+            for name, cams in reports:
+                if cams:
+                    ps, l1 = tr.evaluate(cams)
+                    say("\n[ITER {}] Evaluating {}: L1 {} PSNR {}".format(it, name, l1, ps))
+        if it in args.save_iterations:
+            say("\n[ITER {}] Saving Gaussians".format(it))
+            scene.save(it)
+        if it in args.checkpoint_iterations:
+            say("\n[ITER {}] Saving Checkpoint".format(it))
+            torch.save((model.capture(), it), os.path.join(args.model_path, "chkpnt" + str(it) + ".pth"))
+    torch.cuda.synchronize()
+    say("\nTraining complete: %d iterations, %d points, %.1f s." % (tr.iteration - first_iter, model.P, time.perf_counter() - t0))
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())
