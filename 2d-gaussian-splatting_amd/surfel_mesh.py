@@ -347,14 +347,27 @@ class GaussianExtractor:
         return TriangleMesh(verts, tris, cols)
 
     @torch.no_grad()
-    def export_image(self, path):
-        """utils/mesh_utils.py:282-292 without vis/: path/renders/%05d.png from rgbmaps and path/gt/%05d.png from original_image[0:3],
-        quantised as save_img_u8 does (render_utils.py:270-275): NaN -> 0, clip to [0, 1], times 255, truncated to uint8.  What
-        surfel_metrics.evaluate reads (METRICS.md)."""
-        from PIL import Image
+    def export_image(self, path, vis=False):
+        """utils/mesh_utils.py:282-292: path/renders/%05d.png from rgbmaps and path/gt/%05d.png from original_image[0:3], quantised as
+        save_img_u8 does (render_utils.py:270-275): NaN -> 0, clip to [0, 1], times 255, truncated to uint8.  What
+        surfel_metrics.evaluate reads (METRICS.md).  vis=False leaves vis/ out and converts on the host; vis=True adds
+        path/vis/depth_%05d.tiff (float32, save_img_f32's values) and takes every file through the device-side conversion and the
+        writer threads of surfel_path (RENDER.md): the same pixels."""
         render_path, gts_path = os.path.join(path, "renders"), os.path.join(path, "gt")
         os.makedirs(render_path, exist_ok=True)
         os.makedirs(gts_path, exist_ok=True)
+        if vis:
+            import surfel_path
+            vis_path = os.path.join(path, "vis")
+            os.makedirs(vis_path, exist_ok=True)
+            dev = self.background.device
+            with surfel_path.FrameWriter() as fw:
+                for idx, cam in enumerate(self.viewpoint_stack):
+                    fw.submit(os.path.join(gts_path, "%05d.png" % idx), surfel_path.quantize_u8(cam.original_image[0:3].to(dev)))
+                    fw.submit(os.path.join(render_path, "%05d.png" % idx), surfel_path.quantize_u8(self.rgbmaps[idx]))
+                    fw.submit(os.path.join(vis_path, "depth_%05d.tiff" % idx), self.depthmaps[idx][0])
+            return
+        from PIL import Image
         for idx, cam in enumerate(self.viewpoint_stack):
             for img, folder in ((cam.original_image[0:3], gts_path), (self.rgbmaps[idx], render_path)):
                 a = img.detach().permute(1, 2, 0).cpu().numpy()
@@ -420,9 +433,10 @@ def _scene_cameras(args, gaussians, it):
     return scene.getTrainCameras(), scene.getTestCameras()
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="TSDF mesh of a trained model (render.py's mesh step), bounded or --unbounded. Unlike the reference, which "
-                                             "fuses only the training split, every camera in cameras.json is fused.")
+                                             "fuses only the training split, every camera in cameras.json is fused.  --render_path adds "
+                                             "render.py's trajectory mode (RENDER.md).")
     ap.add_argument("-m", "--model_path", required=True)
     ap.add_argument("--iteration", default=-1, type=int)
     ap.add_argument("--voxel_size", default=-1.0, type=float, help="Mesh: voxel size for TSDF (default depth_trunc / mesh_res)")
@@ -436,7 +450,18 @@ def main(argv=None):
     ap.add_argument("--budget_gb", default=DEFAULT_BUDGET / 2 ** 30, type=float, help="byte budget of the TSDF volume (GiB)")
     ap.add_argument("-s", "--source_path", default=None, help="the capture the model was trained on: cameras and ground-truth images come from it "
                     "(surfel_scene.Scene, with the model's cfg_args), only the training split is fused, and renders / gt of both splits are exported")
-    args = ap.parse_args(argv)
+    ap.add_argument("--skip_train", action="store_true", help="with -s: do not export the training split's renders / gt")
+    ap.add_argument("--skip_test", action="store_true", help="with -s: do not export the test split's renders / gt")
+    ap.add_argument("--skip_mesh", action="store_true", help="do not extract a mesh")
+    ap.add_argument("--render_path", action="store_true", help="render an elliptical fly-through of the training cameras (the capture's with -s, "
+                    "cameras.json otherwise) into MODEL/traj/ours_N: renders/, vis/depth_*.tiff, video/depth/")
+    ap.add_argument("--n_frames", default=240, type=int, help="Path: number of frames of --render_path")
+    ap.add_argument("--vis_normals", action="store_true", help="Path: also write vis/normal_*.png")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     import surfel_io
     import surfel_model
     from surfel_render import render
@@ -455,10 +480,17 @@ def main(argv=None):
     out = os.path.join(args.model_path, "train", "ours_%d" % it)
     os.makedirs(out, exist_ok=True)
     if args.source_path is not None:      # render.py:68-84: renders (at the trained SH degree) / gt of both splits, where surfel_metrics.py looks for them
-        for split, split_cams in (("train", cams), ("test", test_cams)):
-            if split_cams:
+        for split, split_cams, skip in (("train", cams, args.skip_train), ("test", test_cams, args.skip_test)):
+            if split_cams and not skip:
                 ext.reconstruction(split_cams)
                 ext.export_image(os.path.join(args.model_path, split, "ours_%d" % it))
+    if args.render_path:      # render.py:73-84, at the trained SH degree
+        import surfel_path
+        traj_dir = os.path.join(args.model_path, "traj", "ours_%d" % it)
+        surfel_path.render_path(gaussians, cams, render, pipe, ext.background, traj_dir, n_frames=args.n_frames, vis_normals=args.vis_normals)
+        print("trajectory frames saved at {}".format(traj_dir))
+    if args.skip_mesh:
+        return 0
     gaussians.active_sh_degree = 0      # render.py:91: diffuse colour only
     ext.reconstruction(cams)
     if args.unbounded:

@@ -170,6 +170,11 @@ SIGNATURES = {
         "surfel_scene_to_float": (_i, _i, _i, _i, _d, _d, _d, _s),
         "surfel_scene_composite": (_i, _i, _i, _i, _d, _d, _s),
     },
+    "surfel_vis.h": {
+        "surfel_vis_quantize": (_i, _i, _i, _i, _d, _f, _f, _d, _s),
+        "surfel_vis_order_stats": (_i, _i64, _d, _i, _i64p, _d, _d, _i64, _s),
+        "surfel_vis_depth_turbo": (_i, _i, _i, _d, _f64, _f64, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -178,6 +183,7 @@ EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])
 TNT_EXPORTS = list(SIGNATURES["surfel_eval_tnt.h"])
 METRICS_EXPORTS = list(SIGNATURES["surfel_metrics.h"])
 SCENE_EXPORTS = list(SIGNATURES["surfel_scene.h"])
+VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 
