@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(MT) mesh_prepare_kernel(int n, const float* __
     const int i = blockIdx.x * MT + threadIdx.x;
     if (i >= n) return;
     float d = depth[i];
-    if (d > depth_trunc || (mask && mask[i] < 0.5f)) d = 0.f;
+    if (!(d <= depth_trunc) || (mask && mask[i] < 0.5f)) d = 0.f;      // (NaN compares false: a hole too)
     dout[i] = d;
     uint32_t packed = 0;
     for (int c = 0; c < 3; c++) {
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(MT) mesh_integrate_kernel(Vol v, int H, int W,
         if (!(uf >= 0.f && vf >= 0.f && uf < (float)W && vf < (float)H)) continue;
         const int pix = (int)vf * W + (int)uf;
         const float d = depth[pix];
-        if (d == 0.f) continue;
+        if (!(d > 0.f)) continue;      // valid means d > 0, as in pixel_blocks: zero, negative and NaN depths are holes
         const float a = (uf - k.cx) / k.fx, b = (vf - k.cy) / k.fy;
         const float sdf = (d - pz) * sqrtf(1.f + a * a + b * b);
         if (sdf <= -v.trunc) continue;
@@ -343,25 +343,25 @@ void scan_u32(uint32_t* a, int64_t n, uint32_t* scratch, hipStream_t st) {
 }
 
 // ---- connected components over shared edges -------------------------------------------------------------------------------
-__global__ void __launch_bounds__(MT) edge_keys_kernel(int64_t F, const int32_t* __restrict__ tris, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
-    const int64_t e = (int64_t)blockIdx.x * MT + threadIdx.x;
-    if (e >= 3 * F) return;
-    const int64_t t = e / 3;
-    const int j = (int)(e % 3);
-    const uint32_t a = (uint32_t)tris[3 * t + j], b = (uint32_t)tris[3 * t + (j + 1) % 3];
-    key[e] = a > b ? a : b;      // the low half of the (min, max) key: sorted first
-    val[e] = (uint32_t)e;
-}
-
-__device__ inline uint64_t edge_key(const int32_t* tris, uint32_t e) {
+// (min, max) key of edge e; an edge with an endpoint outside [0, V) (a negative id is a large unsigned one) gets the key (V, V), which
+// sorts behind every valid group and links nothing
+__device__ inline uint64_t edge_key(const int32_t* tris, uint32_t e, uint32_t V) {
     const uint32_t t = e / 3, j = e % 3;
     const uint32_t a = (uint32_t)tris[3 * t + j], b = (uint32_t)tris[3 * t + (j + 1) % 3];
+    if (a >= V || b >= V) return (uint64_t)V << 32 | V;
     return a < b ? ((uint64_t)a << 32 | b) : ((uint64_t)b << 32 | a);
 }
 
-__global__ void __launch_bounds__(MT) edge_hi_kernel(int64_t n, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val, uint32_t* __restrict__ key) {
+__global__ void __launch_bounds__(MT) edge_keys_kernel(int64_t F, uint32_t V, const int32_t* __restrict__ tris, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const int64_t e = (int64_t)blockIdx.x * MT + threadIdx.x;
+    if (e >= 3 * F) return;
+    key[e] = (uint32_t)edge_key(tris, (uint32_t)e, V);      // the low half of the (min, max) key: sorted first
+    val[e] = (uint32_t)e;
+}
+
+__global__ void __launch_bounds__(MT) edge_hi_kernel(int64_t n, uint32_t V, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val, uint32_t* __restrict__ key) {
     const int64_t k = (int64_t)blockIdx.x * MT + threadIdx.x;
-    if (k < n) key[k] = (uint32_t)(edge_key(tris, val[k]) >> 32);
+    if (k < n) key[k] = (uint32_t)(edge_key(tris, val[k], V) >> 32);
 }
 
 __device__ inline int32_t uf_find(const int32_t* parent, int32_t x) {
@@ -371,10 +371,11 @@ __device__ inline int32_t uf_find(const int32_t* parent, int32_t x) {
 }
 
 // hooking: the larger root goes under the smaller, so every cluster's root ends as its smallest triangle id
-__global__ void __launch_bounds__(MT) uf_hook_kernel(int64_t n, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val, int32_t* parent) {
+__global__ void __launch_bounds__(MT) uf_hook_kernel(int64_t n, uint32_t V, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val, int32_t* parent) {
     const int64_t k = (int64_t)blockIdx.x * MT + threadIdx.x;
     if (k == 0 || k >= n) return;
-    if (edge_key(tris, val[k]) != edge_key(tris, val[k - 1])) return;
+    const uint64_t key = edge_key(tris, val[k], V);
+    if (key >> 32 == V || key != edge_key(tris, val[k - 1], V)) return;      // (an edge with an id out of range links nothing)
     int32_t a = (int32_t)(val[k] / 3), b = (int32_t)(val[k - 1] / 3);
     while (true) {
         a = uf_find(parent, a); b = uf_find(parent, b);
@@ -590,14 +591,16 @@ int surfel_tsdf_extract(const surfel_tsdf_volume* v, float* verts, float* colors
     return launched("mesh_emit_kernel");
 }
 
+// Edges with a vertex id outside [0, V) carry the key (V, V): they sort behind every valid group and uf_hook_kernel skips them, so
+// they link nothing and cannot come between two equal valid edges.
 int surfel_mesh_clusters(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F, const int32_t* tris, int32_t* label, int32_t* size, void* stream) {
     if (!alloc || V < 0 || F < 0 || (F > 0 && (!tris || !label || !size))) return api_fail(SURFEL_E_INVALID, "mesh_clusters: bad arguments");
     if (F == 0) return 0;
     const int64_t n = 3 * F;
     if (n >= ((int64_t)1 << 30) || V >= ((int64_t)1 << 31)) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: more than 2^30 triangle edges");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < V) bits++;
+    int bits = 1;      // key bits: ids 0 .. V - 1 and the key V of the edges with an id out of range
+    while (bits < 32 && ((int64_t)1 << bits) <= V) bits++;
     uint32_t* ka = take<uint32_t>(alloc, user, n);
     uint32_t* va = take<uint32_t>(alloc, user, n);
     uint32_t* kb = take<uint32_t>(alloc, user, n);
@@ -606,16 +609,16 @@ int surfel_mesh_clusters(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F
     void* scratch = alloc(user, radix_sort_scratch_bytes((size_t)n));
     if (!ka || !va || !kb || !vb || !parent || !scratch) return api_fail(SURFEL_E_ALLOC, "mesh_clusters: allocator returned NULL");
     // (min, max) keys as two stable LSD sorts of 32-bit halves: max first, then min
-    hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, tris, ka, va);
+    hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, (uint32_t)V, tris, ka, va);
     int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, bits, scratch, st);
     if (r < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
     uint32_t* k1 = r ? kb : ka; uint32_t* v1 = r ? vb : va; uint32_t* k2 = r ? ka : kb; uint32_t* v2 = r ? va : vb;
-    hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, tris, v1, k1);
+    hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, v1, k1);
     r = radix_sort_pairs_u32(k1, v1, k2, v2, (size_t)n, 0, bits, scratch, st);
     if (r < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
     const uint32_t* vs = r ? v2 : v1;
     hipLaunchKernelGGL(uf_init_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, size);
-    hipLaunchKernelGGL(uf_hook_kernel, dim3(grid(n)), dim3(MT), 0, st, n, tris, vs, parent);
+    hipLaunchKernelGGL(uf_hook_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, vs, parent);
     hipLaunchKernelGGL(uf_jump_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, label);
     hipLaunchKernelGGL(uf_size_kernel, dim3(grid(F)), dim3(MT), 0, st, F, label, size);
     return launched("uf_size_kernel");

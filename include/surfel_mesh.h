@@ -66,8 +66,9 @@ int64_t surfel_tsdf_table_bytes(const surfel_tsdf_volume* vol);
 int64_t surfel_tsdf_block_bytes(void);
 
 /*
- * One view's fusion inputs from render(): depth_out[H,W] = surf_depth, or 0 where it exceeds depth_trunc or where mask[H,W]
- * (gt_alpha_mask, NULL = none) is < 0.5; rgba_out[H,W] = (uint8)(clamp(rgb[3,H,W], 0, 1) * 255) packed r | g << 8 | b << 16.
+ * One view's fusion inputs from render(): depth_out[H,W] = surf_depth, or 0 where it is not <= depth_trunc (larger, or NaN) or where
+ * mask[H,W] (gt_alpha_mask, NULL = none) is < 0.5; rgba_out[H,W] = (uint8)(clamp(rgb[3,H,W], 0, 1) * 255) packed r | g << 8 | b << 16.
+ * For surfel_tsdf_mark and surfel_tsdf_integrate a depth is valid when it is > 0: zero, negative and NaN depths are holes.
  */
 int surfel_mesh_prepare_view(int H, int W, const float* surf_depth, const float* rgb, const float* mask, float depth_trunc, float* depth_out,
                              uint32_t* rgba_out, void* stream);
@@ -88,7 +89,9 @@ int surfel_tsdf_extract(const surfel_tsdf_volume* vol, float* verts, float* colo
 
 /*
  * Edge-connected triangle clusters: label[F] = smallest triangle id of the triangle's cluster, size[F] = triangles in the cluster
- * whose label is that id (0 for every other id).  Scratch through `alloc`.
+ * whose label is that id (0 for every other id).  Two triangles are connected when they share an unordered pair of vertex ids,
+ * both in [0, V); an edge with an id outside [0, V) links nothing (it sorts behind every valid edge under the key V) and leaves the
+ * other edges of its triangle as they are.  Scratch through `alloc`.
  */
 int surfel_mesh_clusters(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F, const int32_t* tris, int32_t* label, int32_t* size,
                          void* stream);

@@ -88,10 +88,14 @@ def _pixel_f32(g, cam, voxel_size):
     return u, v
 
 
-def fuse(views, voxel_size, sdf_trunc):
-    """views: [(depth [H,W] (0 = invalid, already truncated / masked), rgb8 [H,W,3] uint8, camera block [16])].  fp64 integration
-    (MESH.md §Integration) over the fp32 allocation.  Returns dict(coords, tsdf, rgb, weight, exempt)."""
+def fuse(views, voxel_size, sdf_trunc, table=None):
+    """views: [(depth [H,W] (valid means d > 0; already truncated / masked), rgb8 [H,W,3] uint8, camera block [16])].  fp64 integration
+    (MESH.md §Integration) over the fp32 allocation.  table = (origin, dims) in blocks: only blocks inside it exist (None: no bound).
+    Returns dict(coords, tsdf, rgb, weight, exempt)."""
     per_view = [touched_blocks(d, c, voxel_size, sdf_trunc) for d, _, c in views]
+    if table is not None:
+        lo, hi = np.asarray(table[0], np.int64), np.asarray(table[0], np.int64) + np.asarray(table[1], np.int64)
+        per_view = [{b for b in blocks if np.all(np.asarray(b) >= lo) and np.all(np.asarray(b) < hi)} for blocks in per_view]
     allb = sorted(set().union(*per_view), key=lambda b: (b[2], b[1], b[0]))      # table order: x fastest
     coords = np.array(allb, np.int64).reshape(-1, 3)
     index = {b: k for k, b in enumerate(allb)}
@@ -118,7 +122,8 @@ def fuse(views, voxel_size, sdf_trunc):
         ok &= (u >= 0) & (v >= 0) & (u < W) & (v < H)
         ui, vi = np.where(ok, u, 0).astype(np.int64), np.where(ok, v, 0).astype(np.int64)
         d = depth.astype(np.float64)[vi, ui]
-        ok &= d != 0
+        ok &= d > 0      # valid means d > 0: zero, negative and NaN depths are holes, as in touched_blocks
+        d = np.where(ok, d, 1.0)
         sdf = (d - p[:, 2]) * np.sqrt(1 + ((u - cx) / fx) ** 2 + ((v - cy) / fy) ** 2)
         exempt[sel[near]] = True
         exempt[sel[ok & (np.abs(sdf + tr) < 1e-6)]] = True
@@ -134,6 +139,23 @@ def fuse(views, voxel_size, sdf_trunc):
 
 
 # ------------------------------------------------------------------------------------------------ marching cubes
+def cube_cases(coords, tsdf, weight):
+    """(valid [n] bool, case [n] int64) of the cube at every voxel: valid when all 8 corners are allocated with w > 0; bit c of the
+    case is set when corner c (x = c & 1, y = c >> 1 & 1, z = c >> 2) has tsdf < 0; 0 where the cube is not valid."""
+    coords = np.asarray(coords, np.int64).reshape(-1, 3)
+    g = voxel_coords(coords)
+    look = Lookup(coords)
+    okv = weight > 0
+    inside = tsdf < 0
+    valid = np.ones(len(g), bool)
+    case = np.zeros(len(g), np.int64)
+    for c in range(8):
+        i = look(g + np.array([c & 1, (c >> 1) & 1, (c >> 2) & 1], np.int64))
+        valid &= (i >= 0) & okv[np.maximum(i, 0)]
+        case |= np.where((i >= 0) & inside[np.maximum(i, 0)], 1, 0) << c
+    return valid, np.where(valid, case, 0)
+
+
 def marching_cubes(coords, tsdf, weight, rgb, voxel_size):
     """MESH.md §Extraction on a block-sparse volume.  Returns (verts [V,3] fp64, colors [V,3], tris [F,3] int64) in the library's order."""
     coords = np.asarray(coords, np.int64).reshape(-1, 3)
@@ -146,14 +168,7 @@ def marching_cubes(coords, tsdf, weight, rgb, voxel_size):
     def at(off):
         return look(g + np.asarray(off, np.int64))
 
-    corner = [at((c & 1, (c >> 1) & 1, (c >> 2) & 1)) for c in range(8)]
-    valid = np.ones(n, bool)
-    case = np.zeros(n, np.int64)
-    for c in range(8):
-        i = corner[c]
-        valid &= (i >= 0) & okv[np.maximum(i, 0)]
-        case |= np.where((i >= 0) & inside[np.maximum(i, 0)], 1, 0) << c
-    case = np.where(valid, case, 0)
+    valid, case = cube_cases(coords, tsdf, weight)
     mask = np.zeros((n, 3), bool)
     for a in range(3):
         e = np.eye(3, dtype=np.int64)[a]
@@ -200,6 +215,71 @@ def sphere_volume(radius_vox, center_vox, nblocks):
     g = voxel_coords(coords) + 0.5
     sdf = np.linalg.norm(g - np.asarray(center_vox, np.float64), axis=1) - radius_vox
     return coords, np.clip(sdf / 4.0, -1, 1), np.ones(len(g)), np.full((len(g), 3), 128.0)
+
+
+# ------------------------------------------------------------------------------------------------ post-processing (MESH.md §Post-processing)
+def clusters(tris, V):
+    """(label [F], size [F]) int64.  Two triangles are adjacent when they share an unordered vertex pair {a, b} with both ids in
+    [0, V) (whatever the winding; (a, a) counts); label[t] = smallest triangle id of t's connected set, size[r] = triangles of the
+    set at its root id r and 0 elsewhere.  An edge with an id outside [0, V) links nothing.  A dictionary of edges and a union-find."""
+    tris = np.asarray(tris, np.int64).reshape(-1, 3)
+    F = len(tris)
+    parent = list(range(F))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    first = {}
+    for t, tri in enumerate(tris.tolist()):
+        for a, b in ((tri[0], tri[1]), (tri[1], tri[2]), (tri[2], tri[0])):
+            if not (0 <= a < V and 0 <= b < V):
+                continue
+            o = first.setdefault((min(a, b), max(a, b)), t)
+            ra, rb = find(o), find(t)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)      # the smaller id stays root
+    label = np.array([find(t) for t in range(F)], np.int64).reshape(F)
+    return label, np.bincount(label, minlength=F).astype(np.int64)
+
+
+def post_threshold(size, k):
+    """max(k-th largest cluster size, 50); 50 with fewer than k clusters.  size as clusters() returns it (0 at non-root ids)."""
+    counts = sorted((int(s) for s in np.asarray(size).reshape(-1) if s > 0), reverse=True)
+    return max(counts[k - 1] if 1 <= k <= len(counts) else 0, 50)
+
+
+def filter_mesh(verts, cols, tris, label, size, threshold):
+    """(verts, cols, tris) after the filter: a triangle is kept when size[label[t]] >= threshold and its ids lie in [0, V); a vertex
+    is kept when a kept triangle references it (one that repeats an index too); kept triangles that repeat an index are dropped
+    last.  Order is preserved, floats are copied bit for bit, triangle ids are renumbered to the kept vertices."""
+    verts, cols = np.asarray(verts), np.asarray(cols)
+    tris = np.asarray(tris, np.int64).reshape(-1, 3)
+    label, size = np.asarray(label, np.int64), np.asarray(size, np.int64)
+    V = len(verts)
+    keep = (size[label] >= threshold) & np.all((tris >= 0) & (tris < V), axis=1)
+    vref = np.zeros(V, bool)
+    vref[tris[keep].reshape(-1)] = True
+    vpos = np.cumsum(vref) - vref
+    t = tris[keep]
+    t = t[(t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 0] != t[:, 2])]
+    return verts[vref], cols[vref], vpos[t].reshape(-1, 3)
+
+
+# name: (tris, V, label worked out by hand) -- the small cluster cases the CPU tests pin the reference to and the GPU tests rerun
+HAND_CLUSTERS = {
+    "single": ([(0, 1, 2)], 3, [0]),
+    "bow_tie": ([(0, 1, 2), (2, 3, 4)], 5, [0, 1]),                                        # one shared vertex is no edge
+    "edge_same_winding": ([(0, 1, 2), (0, 1, 3)], 4, [0, 0]),
+    "edge_opposite_winding": ([(0, 1, 2), (1, 0, 3)], 4, [0, 0]),
+    "fan_of_5": ([(0, 1, 2), (1, 0, 3), (0, 1, 4), (5, 0, 1), (1, 6, 0)], 7, [0] * 5),      # non-manifold: five on edge 0-1
+    "duplicate": ([(0, 1, 2), (0, 1, 2)], 3, [0, 0]),
+    "repeated_index": ([(3, 4, 5), (0, 0, 1), (2, 1, 0)], 6, [0, 1, 1]),                   # (a, a, b) has the edge a-b
+    # V = 16: (5, 25) has an id out of range and 25 & 15 = 9, so on 4 key bits it would sort between the two (5, 9) edges
+    "bad_id_alias": ([(5, 9, 1), (5, 25, 3), (9, 5, 2)], 16, [0, 1, 0]),
+}
 
 
 # ------------------------------------------------------------------------------------------------ mesh checks

@@ -111,6 +111,92 @@ def test_oracle_tsdf_fronto_parallel_plane():
     assert np.allclose(vol["rgb"][m], 200.0)
 
 
+# ------------------------------------------------------------------------------------------------ post-processing references
+@pytest.mark.parametrize("name", sorted(O.HAND_CLUSTERS))
+def test_oracle_clusters_hand_cases(name):
+    tris, V, expect = O.HAND_CLUSTERS[name]
+    label, size = O.clusters(tris, V)
+    assert label.tolist() == expect
+    assert size.tolist() == [expect.count(t) for t in range(len(tris))]      # the count at root ids, 0 elsewhere
+
+
+def test_oracle_clusters_counts():
+    n = {name: len(set(expect)) for name, (_, _, expect) in O.HAND_CLUSTERS.items()}
+    assert n == dict(single=1, bow_tie=2, edge_same_winding=1, edge_opposite_winding=1, fan_of_5=1, duplicate=1, repeated_index=2,
+                     bad_id_alias=2)
+    # an edge with an id out of range changes nothing for the others: -1, V and V + id alike
+    base = [(0, 1, 2), (2, 1, 3), (4, 5, 6)]
+    for bad in (-1, 7, 7 + 1, 2 ** 31 - 1):
+        label, size = O.clusters(base + [(1, 2, bad), (bad, 5, 4), (bad, bad, bad)], 7)
+        assert label.tolist() == [0, 0, 2, 0, 2, 5] and size.tolist() == [3, 0, 2, 0, 0, 1]
+    label, size = O.clusters(np.zeros((0, 3), np.int64), 4)
+    assert label.shape == (0,) and size.shape == (0,)
+
+
+def _six_triangle_mesh():
+    """10 vertices, 6 triangles.  Cluster A: T0, T1 (edge 1-2), T3 = (1, 1, 3) (edge 1-3 of T1) and T5 = (7, 1, 1) (the pair {1, 1} of
+    T3); cluster B: T2, T4 (edge 4-5).  Vertex 7 is referenced by the degenerate T5 alone, vertex 9 by nothing."""
+    tris = np.array([(0, 1, 2), (2, 1, 3), (4, 5, 6), (1, 1, 3), (5, 4, 8), (7, 1, 1)], np.int64)
+    rng = np.random.default_rng(5)
+    verts = rng.integers(0, 2 ** 32, (10, 3), dtype=np.uint64).astype(np.uint32).view(np.float32)      # any bit pattern, NaNs too
+    cols = rng.integers(0, 2 ** 32, (10, 3), dtype=np.uint64).astype(np.uint32).view(np.float32)
+    return verts, cols, tris
+
+
+def _bits(x):
+    return np.ascontiguousarray(x).view(np.uint32).tolist()
+
+
+def test_oracle_filter_mesh_six_triangles():
+    verts, cols, tris = _six_triangle_mesh()
+    label, size = O.clusters(tris, len(verts))
+    assert label.tolist() == [0, 0, 2, 0, 2, 0] and size.tolist() == [4, 0, 2, 0, 0, 0]
+    # threshold 3: B (2 triangles) goes with its vertices 4, 5, 6, 8; 7 stays through T5; 9 is unreferenced; T3 and T5 leave last
+    v, c, t = O.filter_mesh(verts, cols, tris, label, size, 3)
+    assert _bits(v) == _bits(verts[[0, 1, 2, 3, 7]]) and _bits(c) == _bits(cols[[0, 1, 2, 3, 7]])
+    assert v.dtype == np.float32 and t.tolist() == [[0, 1, 2], [2, 1, 3]]
+    # threshold 2: >= keeps B at exactly its size; only vertex 9 goes
+    v, c, t = O.filter_mesh(verts, cols, tris, label, size, 2)
+    assert _bits(v) == _bits(verts[:9]) and _bits(c) == _bits(cols[:9])
+    assert t.tolist() == [[0, 1, 2], [2, 1, 3], [4, 5, 6], [5, 4, 8]]
+    v, c, t = O.filter_mesh(verts, cols, tris, label, size, 5)
+    assert v.shape == (0, 3) and c.shape == (0, 3) and t.shape == (0, 3)
+    # T1 with an id out of range: it is dropped whatever its cluster, its edge 2-1 still links it to T0, its other edges link nothing,
+    # so T3 and T5 form a cluster of their own; vertex 3 now survives through the degenerate T3 alone
+    tris[1] = (2, 1, 10)
+    label, size = O.clusters(tris, len(verts))
+    assert label.tolist() == [0, 0, 2, 3, 2, 3] and size.tolist() == [2, 0, 2, 2, 0, 0]
+    v, c, t = O.filter_mesh(verts, cols, tris, label, size, 2)
+    assert _bits(v) == _bits(verts[:9]) and t.tolist() == [[0, 1, 2], [4, 5, 6], [5, 4, 8]]
+
+
+def test_oracle_post_threshold():
+    size = np.array([300, 0, 0, 120, 120, 0, 120, 60, 0, 7])      # clusters of 300, 120, 120, 120, 60, 7
+    assert [O.post_threshold(size, k) for k in (1, 2, 3, 4, 5)] == [300, 120, 120, 120, 60]      # ties at the k-th place
+    assert O.post_threshold(size, 6) == 50                       # the 6th largest is 7: the floor of 50 holds
+    assert O.post_threshold(size, 7) == 50 and O.post_threshold(size, 1000) == 50      # fewer than k clusters
+    assert O.post_threshold(np.array([49, 0, 12, 3]), 1) == 50   # all clusters below 50
+    assert O.post_threshold(np.zeros(0, np.int64), 1) == 50
+
+
+def test_oracle_fuse_invalid_depths_are_holes():
+    W, H, vs, tr = 32, 24, 0.05, 0.25
+    cam = np.zeros(16, np.float32)
+    cam[[0, 5, 10]] = 1.0
+    cam[12:] = [25.0, 25.0, (W - 1) / 2, (H - 1) / 2]
+    depth = np.full((H, W), 2.0, np.float32)
+    rgb8 = np.full((H, W, 3), 200, np.uint8)
+    bad = depth.copy()
+    hole = depth.copy()
+    for k, x in enumerate((np.nan, -np.inf, -1e-9, -1.0, 0.0)):
+        bad[4:8, 4 * k + 2:4 * k + 5] = x
+        hole[4:8, 4 * k + 2:4 * k + 5] = 0.0
+    a, b = O.fuse([(bad, rgb8, cam)], vs, tr), O.fuse([(hole, rgb8, cam)], vs, tr)
+    assert np.array_equal(a["coords"], b["coords"]) and np.array_equal(a["weight"], b["weight"])
+    assert np.array_equal(a["tsdf"], b["tsdf"]) and np.isfinite(a["tsdf"]).all()
+    assert (a["weight"] > 0).sum() > 1000
+
+
 # ------------------------------------------------------------------------------------------------ bounding sphere
 def test_bounding_sphere_orbit():
     sys.path.insert(0, os.path.join(REPO, "2d-gaussian-splatting_amd"))
