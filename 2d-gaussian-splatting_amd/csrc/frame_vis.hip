@@ -7,50 +7,13 @@
 
 #include "../../include/surfel_vis.h"
 #include "train_kernels.h"
+#include "vis_pixels.h"
 #include "vis_turbo_table.h"
 
 namespace surfel {
 
 constexpr int VT = 256;      // threads per workgroup
-constexpr int PX = 4;        // consecutive pixels per lane: 16 B of every plane in, 4 C bytes out
 constexpr int NR = SURFEL_VIS_MAX_RANKS;
-
-// ---- 4 pixels in, 4 C bytes out --------------------------------------------------------------------------------------------------------
-// v[0..3] <- p[i .. i + 3]: one 16-byte load where the address allows it (the same answer for every lane of a plane: lanes are 16 B
-// apart), four 4-byte loads otherwise; nothing at or behind p[n] is read
-__device__ __forceinline__ void load4(const float* __restrict__ p, int64_t i, int64_t n, float (&v)[PX]) {
-    const float* q = p + i;
-    if (i + PX <= n && (reinterpret_cast<uintptr_t>(q) & 15) == 0) {
-        const float4 f = *reinterpret_cast<const float4*>(q);
-        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < PX; j++) v[j] = i + j < n ? q[j] : 0.0f;
-    }
-}
-
-// the first nbytes (<= 4 NW) bytes of the little-endian words w[] to q: whole dwords where q is 4-byte aligned and all bytes are there;
-// otherwise the bytes up to the next dword boundary one by one, then whole dwords cut out of w[] at that byte offset, then the rest
-// one by one.  Nothing outside [q, q + nbytes) is written.
-template <int NW>
-__device__ __forceinline__ void store_bytes(uint8_t* __restrict__ q, int nbytes, const uint32_t (&w)[NW]) {
-    const int a = (int)(reinterpret_cast<uintptr_t>(q) & 3);
-    if (a == 0 && nbytes == 4 * NW) {
-#pragma unroll
-        for (int k = 0; k < NW; k++) reinterpret_cast<uint32_t*>(q)[k] = w[k];
-        return;
-    }
-    const int head = min((4 - a) & 3, nbytes);
-    const int nd = (nbytes - head) >> 2;
-#pragma unroll
-    for (int k = 0; k < NW; k++) {
-        const uint64_t pair = (uint64_t)w[k] | ((uint64_t)(k + 1 < NW ? w[k + 1] : 0u) << 32);
-        if (k < nd) *reinterpret_cast<uint32_t*>(q + head + 4 * k) = (uint32_t)(pair >> (8 * head));
-    }
-#pragma unroll
-    for (int b = 0; b < 4 * NW; b++)
-        if (b < nbytes && (b < head || b >= head + 4 * nd)) q[b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
-}
 
 // save_img_u8's arithmetic on one value (fp32, one rounding per operation)
 __device__ __forceinline__ uint32_t quant8(float v, float scale, float bias) {
@@ -110,18 +73,6 @@ __global__ void __launch_bounds__(VT) vis_depth_turbo_kernel(int64_t hw, const f
 }
 
 // ---- order statistics ------------------------------------------------------------------------------------------------------------------
-// key: unsigned order = numpy's sort order of the floats (every NaN is the largest key; -0 sorts directly below +0)
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    if (v != v) return 0xffffffffu;
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float order_value(uint32_t key) {
-    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((key >> 31) ? (key ^ 0x80000000u) : ~key);
-}
-
 // selection state behind the histograms in the caller's scratch.  prefix[j]: the key bytes of rank j decided so far; rank[j]: its rank
 // among the elements that share them.  Ranks whose prefixes are equal (neighbouring order statistics, mostly) share one histogram:
 // slot[j] indexes uprefix[0 .. nuniq).

@@ -175,6 +175,10 @@ SIGNATURES = {
         "surfel_vis_order_stats": (_i, _i64, _d, _i, _i64p, _d, _d, _i64, _s),
         "surfel_vis_depth_turbo": (_i, _i, _i, _d, _f64, _f64, _d, _s),
     },
+    "surfel_view.h": {
+        "surfel_view_scalar": (_i, _i, _i, _d, _d, _d, _i64, _s),
+        "surfel_view_gradient": (_i, _i, _i, _d, _f, _f, _d, _d, _i64, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -184,6 +188,7 @@ TNT_EXPORTS = list(SIGNATURES["surfel_eval_tnt.h"])
 METRICS_EXPORTS = list(SIGNATURES["surfel_metrics.h"])
 SCENE_EXPORTS = list(SIGNATURES["surfel_scene.h"])
 VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
+VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

@@ -571,8 +571,20 @@ class Trainer:
             return float(torch.stack(ps).mean()), float(torch.stack(l1).mean())
 
 
-def training(model, cams, opt=None, pipe=None, iterations=None, white_background=False, log_every=0, seed=0):
-    """Run the loop; returns the Trainer (model trained in place).  log_every > 0 prints loss / points / it/s."""
+def viewer_metrics(tr):
+    """What the serve loop sends with every frame (train.py:157-160): the point count and the photometric loss — of the last
+    iteration, read from the device only when a viewer asks, where the reference keeps a running mean with an .item() per step."""
+    return lambda: {"#": int(tr.model.P), "loss": float(tr.last["scalars"][4]) if tr.last else 0.0}
+
+
+def serve_viewer(viewer, tr, source_path=""):
+    """train.py:146-168 after a step: let a connected remote viewer (surfel_view.Viewer) look at the model; a no-op without one."""
+    viewer.serve(tr.model, tr.pipe, tr.background, source_path, viewer_metrics(tr), tr.iteration, tr.opt.iterations)
+
+
+def training(model, cams, opt=None, pipe=None, iterations=None, white_background=False, log_every=0, seed=0, viewer=None):
+    """Run the loop; returns the Trainer (model trained in place).  log_every > 0 prints loss / points / it/s.  viewer: a
+    surfel_view.Viewer that is served after every step (VIEWER.md); None (the default) touches no socket."""
     opt = opt or optimization_params()
     if iterations is not None:
         opt.iterations = iterations
@@ -580,6 +592,8 @@ def training(model, cams, opt=None, pipe=None, iterations=None, white_background
     t0 = time.perf_counter()
     for _ in range(opt.iterations):
         tr.step()
+        if viewer is not None:
+            serve_viewer(viewer, tr)
         if log_every and tr.iteration % log_every == 0 and tr.rank == 0:
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -595,10 +609,13 @@ _OPTIMIZATION_ARGS = ("iterations", "position_lr_init", "position_lr_final", "po
 
 
 def parse_args(argv=None):
-    """The reference's flags with its defaults (arguments/__init__.py:47-95, train.py:258-265), without the viewer's --ip / --port."""
+    """The reference's flags with its defaults (arguments/__init__.py:47-95, train.py:258-265), without the viewer's --ip / --port:
+    those are parse_viewer_args', which main() lets take its two flags out of the command line first."""
     import argparse
     import os
-    ap = argparse.ArgumentParser(description="Train a 2-D Gaussian surfel model on a COLMAP or Blender capture")
+    ap = argparse.ArgumentParser(description="Train a 2-D Gaussian surfel model on a COLMAP or Blender capture",
+                                 epilog="The remote viewer (VIEWER.md): --port PORT serves it while training, on --ip IP (default 127.0.0.1); "
+                                        "without --port no listener exists.")
     g = ap.add_argument_group("Loading Parameters")
     g.add_argument("--source_path", "-s", default="", type=str)
     g.add_argument("--model_path", "-m", default="", type=str)
@@ -643,6 +660,25 @@ def write_cfg_args(args):
     return path
 
 
+def parse_viewer_args(argv=None):
+    """(viewer flags, the rest of the command line): --ip (default 127.0.0.1) and --port (default: none).  A departure from the
+    reference, which always binds 127.0.0.1:6009: the listener exists only when --port is given, so two runs on one machine do not
+    collide and a run without the flag behaves as it always did."""
+    import argparse
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--ip", type=str, default="127.0.0.1", help="address the remote viewer's listener binds (with --port)")
+    ap.add_argument("--port", type=int, default=None, help="serve the SIBR remote viewer on this port while training (default: no listener)")
+    return ap.parse_known_args(argv)
+
+
+def make_viewer(vargs):
+    """The remote viewer's listener for --port, or None: without the flag no socket object is created."""
+    if vargs.port is None:
+        return None
+    import surfel_view
+    return surfel_view.Viewer(vargs.ip, vargs.port)
+
+
 def main(argv=None):
     """python surfel_trainer.py -s <capture> -m <model folder> [...]: trains, saves point_cloud/iteration_N at the save iterations (the
     last iteration always among them), checkpoints as (capture(), iteration), and reports L1 / PSNR of the test split and of a train
@@ -650,7 +686,8 @@ def main(argv=None):
     import os
     import uuid
     from surfel_scene import Scene
-    args = parse_args(argv)
+    vargs, rest = parse_viewer_args(argv)
+    args = parse_args(rest)
     if not args.model_path:
         args.model_path = os.path.join("./output/", str(uuid.uuid4())[0:10])
     say = (lambda *a, **k: None) if args.quiet else print
@@ -668,10 +705,13 @@ def main(argv=None):
     tr = Trainer(model, scene.getTrainCameras(), opt, pipe, args.white_background, extent=scene.cameras_extent, seed=args.seed, first_iter=first_iter)
     train_cams = scene.getTrainCameras()
     reports = (("test", scene.getTestCameras()), ("train", [train_cams[i % len(train_cams)] for i in range(5, 30, 5)]))
+    viewer = make_viewer(vargs)
     t0 = time.perf_counter()
     while tr.iteration < opt.iterations:
         tr.step()
         it = tr.iteration
+        if viewer is not None:
+            serve_viewer(viewer, tr, args.source_path)
         if it in args.test_iterations:
             for name, cams in reports:
                 if cams:
@@ -683,6 +723,8 @@ def main(argv=None):
         if it in args.checkpoint_iterations:
             say("\n[ITER {}] Saving Checkpoint".format(it))
             torch.save((model.capture(), it), os.path.join(args.model_path, "chkpnt" + str(it) + ".pth"))
+    if viewer is not None:
+        viewer.close()
     torch.cuda.synchronize()
     say("\nTraining complete: %d iterations, %d points, %.1f s." % (tr.iteration - first_iter, model.P, time.perf_counter() - t0))
     return 0
