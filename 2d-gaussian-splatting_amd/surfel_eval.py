@@ -308,6 +308,21 @@ def cull_vertices(vertices, proj, dilated):
     return keep.bool()
 
 
+def compact_kept(verts, tris, keep, vertex_colors=None):
+    """The tail of a vertex cull (shared with surfel_cull): the triangles whose three vertices are kept (keep: bool [V]), then the vertices
+    some kept triangle uses, in their order, with their colours (zeros where the mesh has none) -> (vertices, int32 triangles, colours).
+    verts [V, 3] float32, tris [F, 3] int64 with every index inside [0, V)."""
+    dev = verts.device
+    tkeep = keep[tris].all(dim=1)
+    tris = tris[tkeep]
+    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=dev)
+    used[tris.reshape(-1)] = True
+    remap = torch.cumsum(used.to(torch.int64), 0) - 1
+    cols = vertex_colors[used] if vertex_colors is not None and vertex_colors.shape[0] == verts.shape[0] else \
+        torch.zeros((int(used.sum()), 3), dtype=torch.float32, device=dev)
+    return verts[used], remap[tris].to(torch.int32), cols
+
+
 def cull_mesh(mesh, intrinsics, poses, masks, dilate=24, scale=1.0, offset=0.0):
     """evaluate_single_scene.py:57-99: drop the vertices that some view sees outside its dilated mask, the triangles that lose a vertex
     and the vertices no kept triangle uses (order kept), then vertices * scale + offset.  intrinsics, poses (camera to world): [V, 4, 4]
@@ -316,15 +331,9 @@ def cull_mesh(mesh, intrinsics, poses, masks, dilate=24, scale=1.0, offset=0.0):
     tris = _dev(mesh.triangles, "mesh.triangles").detach().to(torch.int64)
     dev = verts.device
     keep = cull_vertices(verts, projections(intrinsics, poses), dilate_masks(masks, dilate))
-    tkeep = keep[tris].all(dim=1)
-    tris = tris[tkeep]
-    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=dev)
-    used[tris.reshape(-1)] = True
-    remap = torch.cumsum(used.to(torch.int64), 0) - 1
-    cols = mesh.vertex_colors[used] if getattr(mesh, "vertex_colors", None) is not None and mesh.vertex_colors.shape[0] == verts.shape[0] else \
-        torch.zeros((int(used.sum()), 3), dtype=torch.float32, device=dev)
+    kept, tris, cols = compact_kept(verts, tris, keep, getattr(mesh, "vertex_colors", None))
     off = torch.as_tensor(np.broadcast_to(np.asarray(offset, np.float32), (3,)).copy(), device=dev)
-    return TriangleMesh(verts[used] * float(scale) + off, remap[tris].to(torch.int32), cols)
+    return TriangleMesh(kept * float(scale) + off, tris, cols)
 
 
 # ------------------------------------------------------------------------------------------------ command line

@@ -179,6 +179,10 @@ SIGNATURES = {
         "surfel_view_scalar": (_i, _i, _i, _d, _d, _d, _i64, _s),
         "surfel_view_gradient": (_i, _i, _i, _d, _f, _f, _d, _d, _i64, _s),
     },
+    "surfel_cull.h": {
+        "surfel_cull_mesh_depth": (_i64, _a, _u, _i64, _i64, _d, _d, _i, _d, _d, _i, _i, _i, _f, _f, _i, _d, _fp, _s),
+        "surfel_cull_visibility": (_i, _i64, _d, _i, _d, _d, _i, _i, _i, _d, _f, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -189,6 +193,7 @@ METRICS_EXPORTS = list(SIGNATURES["surfel_metrics.h"])
 SCENE_EXPORTS = list(SIGNATURES["surfel_scene.h"])
 VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
 VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
+CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 
