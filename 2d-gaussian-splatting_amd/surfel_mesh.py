@@ -457,7 +457,19 @@ def build_parser():
                     "cameras.json otherwise) into MODEL/traj/ours_N: renders/, vis/depth_*.tiff, video/depth/")
     ap.add_argument("--n_frames", default=240, type=int, help="Path: number of frames of --render_path")
     ap.add_argument("--vis_normals", action="store_true", help="Path: also write vis/normal_*.png")
+    ap.add_argument("--video", action="store_true", help="Path: also write render_traj_{color,depth}.avi (and _normal with --vis_normals): "
+                    "Motion-JPEG encoded on the device (VIDEO.md)")
+    ap.add_argument("--video_only", action="store_true", help="Path: write the videos and none of the per-frame files")
+    ap.add_argument("--video_quality", default=95, type=int, help="Path: JPEG quality of the videos' frames, 1 .. 100")
+    ap.add_argument("--fps", default=60, type=int, help="Path: frame rate of the videos")
     return ap
+
+
+def path_video_args(args):
+    """render_path's video arguments from the CLI's: none at all unless a video was asked for"""
+    if not (args.video or args.video_only):
+        return {}
+    return dict(video=True, video_only=args.video_only, video_quality=args.video_quality, fps=args.fps)
 
 
 def main(argv=None):
@@ -487,7 +499,8 @@ def main(argv=None):
     if args.render_path:      # render.py:73-84, at the trained SH degree
         import surfel_path
         traj_dir = os.path.join(args.model_path, "traj", "ours_%d" % it)
-        surfel_path.render_path(gaussians, cams, render, pipe, ext.background, traj_dir, n_frames=args.n_frames, vis_normals=args.vis_normals)
+        surfel_path.render_path(gaussians, cams, render, pipe, ext.background, traj_dir, n_frames=args.n_frames, vis_normals=args.vis_normals,
+                                **path_video_args(args))
         print("trajectory frames saved at {}".format(traj_dir))
     if args.skip_mesh:
         return 0

@@ -183,6 +183,11 @@ SIGNATURES = {
         "surfel_cull_mesh_depth": (_i64, _a, _u, _i64, _i64, _d, _d, _i, _d, _d, _i, _i, _i, _f, _f, _i, _d, _fp, _s),
         "surfel_cull_visibility": (_i, _i64, _d, _i, _d, _d, _i, _i, _i, _d, _f, _d, _s),
     },
+    "surfel_jpeg.h": {
+        "surfel_jpeg_capacity": (_i64, _i, _i),
+        "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
+        "surfel_jpeg_encode": (_i, _i, _i, _d, _i, _d, _i64, _d, _d, _i64, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -194,6 +199,7 @@ SCENE_EXPORTS = list(SIGNATURES["surfel_scene.h"])
 VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
 VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
+JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

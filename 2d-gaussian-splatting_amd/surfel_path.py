@@ -338,27 +338,75 @@ def _folders(out_dir, names):
 
 
 @torch.no_grad()
-def render_path(gaussians, cameras, render, pipe, background, out_dir, n_frames=240, vis_normals=False, workers=4, timings=None):
-    """render.py:73-84 without the encoder: the elliptical path through `cameras`, rendered frame by frame and written as
+def render_path(gaussians, cameras, render, pipe, background, out_dir, n_frames=240, vis_normals=False, workers=4, timings=None,
+                video=False, video_only=False, video_quality=95, fps=60):
+    """render.py:73-84: the elliptical path through `cameras`, rendered frame by frame and written as
     out_dir/renders/%05d.png (colour), vis/depth_%05d.tiff (surf_depth, float32), video/depth/%05d.png (the depth video's frames:
     turbo of log depth between the 3rd and 97th percentile of frame 0) and, with vis_normals, vis/normal_%05d.png (rend_normal * 0.5 +
     0.5).  Frames are converted on the device and handed to a FrameWriter: the one host wait of the loop is frame 0's depth limits.
-    timings: a dict that receives the loop's host time and the FrameWriter's counters.  Returns the path cameras."""
+    video: also out_dir/render_traj_color.avi, render_traj_depth.avi and, with vis_normals, render_traj_normal.avi (Motion-JPEG at
+    video_quality and fps, VIDEO.md), fed from the very tensors that go to renders/, video/depth/ and vis/normal_*: create_videos'
+    three videos, frame for frame, encoded on the device.  video_only: the videos and none of the per-frame files or folders.
+    timings: a dict that receives the loop's host time and the writers' counters.  Returns the path cameras."""
     traj = generate_path(cameras, n_frames=n_frames)
-    renders, vis, video = _folders(out_dir, ["renders", "vis", "video/depth"])
+    video = video or video_only
+    if video_only:
+        os.makedirs(out_dir, exist_ok=True)
+        renders = vis = depth_dir = None
+    else:
+        renders, vis, depth_dir = _folders(out_dir, ["renders", "vis", "video/depth"])
     lo = hi = None
+    writers = {}
+    fw = None if video_only else FrameWriter(workers=workers)      # (video_only: no encoder threads, no pinned ring)
+
+    def emit(name, frame, folder, pattern, idx):
+        if fw is not None:
+            fw.submit(os.path.join(folder, pattern % idx), frame)
+        if video:
+            if name not in writers:
+                import surfel_video
+                writers[name] = surfel_video.VideoWriter(os.path.join(out_dir, "render_traj_%s.avi" % name), frame.shape[0], frame.shape[1],
+                                                         fps=fps, quality=video_quality)
+            writers[name].add_frame(frame)
+
+    def finish_videos():
+        """every video gets its index and headers; the first error any writer met"""
+        first = None
+        for w in writers.values():
+            try:
+                w.close()
+            except BaseException as e:
+                first = first or e
+        return first
+
     t0 = time.perf_counter()
-    with FrameWriter(workers=workers) as fw:
+    try:
         for idx, cam in enumerate(traj):
             pkg = render(cam, gaussians, pipe, background)
             depth = pkg["surf_depth"][0]
             if idx == 0:
                 lo, hi = depth_limits(depth)
-            fw.submit(os.path.join(renders, "%05d.png" % idx), quantize_u8(pkg["render"]))
-            fw.submit(os.path.join(vis, "depth_%05d.tiff" % idx), depth)
-            fw.submit(os.path.join(video, "%05d.png" % idx), colorize_depth(depth, lo, hi))
+            emit("color", quantize_u8(pkg["render"]), renders, "%05d.png", idx)
+            if fw is not None:
+                fw.submit(os.path.join(vis, "depth_%05d.tiff" % idx), depth)
+            emit("depth", colorize_depth(depth, lo, hi), depth_dir, "%05d.png", idx)
             if vis_normals:
-                fw.submit(os.path.join(vis, "normal_%05d.png" % idx), quantize_u8(pkg["rend_normal"], 0.5, 0.5))
+                emit("normal", quantize_u8(pkg["rend_normal"], 0.5, 0.5), vis, "normal_%05d.png", idx)
         if timings is not None:      # (the time close() then waits for the encoders is the caller's total minus loop_ms)
-            timings.update(loop_ms=(time.perf_counter() - t0) * 1e3, submit_wait_ms=fw.wait_s * 1e3, files=fw.frames, depth_limits=(lo, hi))
+            timings.update(loop_ms=(time.perf_counter() - t0) * 1e3, submit_wait_ms=fw.wait_s * 1e3 if fw else 0.0, files=fw.frames if fw else 0,
+                           depth_limits=(lo, hi))
+            if video:
+                timings.update(video_wait_ms=sum(w.wait_s for w in writers.values()) * 1e3, videos=sorted(writers))
+    except BaseException:
+        if fw is not None:
+            fw._drain()
+        finish_videos()
+        raise
+    try:
+        if fw is not None:
+            fw.close()
+    finally:
+        error = finish_videos()
+    if error is not None:
+        raise error
     return traj

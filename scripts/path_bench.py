@@ -11,6 +11,10 @@ same process; end-to-end frames per second of surfel_path.render_path, files on 
 parent's way in the same process: GaussianExtractor.reconstruction() + export_image() (every fp32 frame kept on the device, copied to the
 host as fp32, quantised in numpy, encoded on one thread).  The two ways write different files per frame (render_path: colour PNG, depth
 TIFF, turbo PNG; export_image: colour PNG, ground-truth PNG); both lists are in the line.
+The video path (VIDEO.md) beside them: jpeg_ms, the device time of one surfel_jpeg_encode of frame 0's colour frame at quality 95 (all
+its launches, scratch from the caching allocator), jpeg_MBps_in against the 3 bytes per pixel it reads, jpeg_bytes, the file's size,
+and video_fps, the same loop with video_only=True and three streams (colour, depth, normal; no per-frame file), AVI files on disk
+included.
 """
 import argparse
 import json
@@ -88,6 +92,13 @@ def case(dev, preset, frames, repeat, warmup, workers, hbm):
         lo, hi = limits if limits[0] > -float("inf") and limits[1] > limits[0] else (0.0, 2.0)
         out["colorize_ms"] = round(event_ms(lambda: SP.colorize_depth(depth, lo, hi, out=rgb8), repeat, warmup), 4)
         out["colorize_GBps"] = gbps(7 * hw, out["colorize_ms"])
+        import surfel_video as SV
+        SP.quantize_u8(rgb, out=rgb8)
+        jbuf, jsize = SV.encode_jpeg(rgb8)
+        out["jpeg_ms"] = round(event_ms(lambda: SV.encode_jpeg(rgb8, out=jbuf, size=jsize), repeat, warmup), 4)
+        out["jpeg_MBps_in"] = round(3 * hw / out["jpeg_ms"] / 1e3, 1)
+        out["jpeg_bytes"] = int(jsize.item())
+        del jbuf
         pin8, pin32 = torch.empty((H, W, 3), dtype=torch.uint8, pin_memory=True), torch.empty((H, W), dtype=torch.float32, pin_memory=True)
 
         def copies():                     # one frame's files: colour, turbo (3 B / pixel each), depth (4 B / pixel)
@@ -114,6 +125,18 @@ def case(dev, preset, frames, repeat, warmup, workers, hbm):
             out["encode_wait_ms"] = round((info_p["submit_wait_ms"] + total - info_p["loop_ms"]) / frames, 3)
             out["path_files_per_frame"] = ["renders/*.png", "vis/depth_*.tiff", "video/depth/*.png"]
             out["path_MB_on_disk"] = round(folder_bytes(os.path.join(tmp, "timed")) / 1e6, 1)
+            for name in ("video_warm", "video_timed"):
+                info_v = {}
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                SP.render_path(model, cams, render, pipe, bg, os.path.join(tmp, name), n_frames=frames, vis_normals=True, video_only=True, timings=info_v)
+                torch.cuda.synchronize()
+                total_v = (time.perf_counter() - t) * 1e3
+            out["video_fps"] = round(frames / total_v * 1e3, 2)
+            out["video_loop_ms_per_frame"] = round(info_v["loop_ms"] / frames, 3)
+            out["video_wait_ms"] = round(info_v["video_wait_ms"] / frames, 3)
+            out["video_files"] = ["render_traj_color.avi", "render_traj_depth.avi", "render_traj_normal.avi"]
+            out["video_MB_on_disk"] = round(folder_bytes(os.path.join(tmp, "video_timed")) / 1e6, 1)
             # ---- the parent's way, same cameras
             ext = surfel_mesh.GaussianExtractor(model, render, pipe)
             torch.cuda.synchronize()
