@@ -347,25 +347,30 @@ class GaussianExtractor:
         return TriangleMesh(verts, tris, cols)
 
     @torch.no_grad()
-    def export_image(self, path, vis=False):
+    def export_image(self, path, vis=False, png="pillow"):
         """utils/mesh_utils.py:282-292: path/renders/%05d.png from rgbmaps and path/gt/%05d.png from original_image[0:3], quantised as
         save_img_u8 does (render_utils.py:270-275): NaN -> 0, clip to [0, 1], times 255, truncated to uint8.  What
         surfel_metrics.evaluate reads (METRICS.md).  vis=False leaves vis/ out and converts on the host; vis=True adds
         path/vis/depth_%05d.tiff (float32, save_img_f32's values) and takes every file through the device-side conversion and the
-        writer threads of surfel_path (RENDER.md): the same pixels."""
+        writer threads of surfel_path (RENDER.md): the same pixels.  png="device" encodes the PNG files on the device (PNG.md) through the
+        same conversion and writer, with or without vis: the same names, files that decode to the same pixels."""
+        if png not in ("pillow", "device"):
+            raise ValueError("export_image: png must be 'pillow' or 'device', got %r" % (png,))
         render_path, gts_path = os.path.join(path, "renders"), os.path.join(path, "gt")
         os.makedirs(render_path, exist_ok=True)
         os.makedirs(gts_path, exist_ok=True)
-        if vis:
+        if vis or png == "device":
             import surfel_path
             vis_path = os.path.join(path, "vis")
-            os.makedirs(vis_path, exist_ok=True)
+            if vis:
+                os.makedirs(vis_path, exist_ok=True)
             dev = self.background.device
-            with surfel_path.FrameWriter() as fw:
+            with surfel_path.FrameWriter(png=png) as fw:
                 for idx, cam in enumerate(self.viewpoint_stack):
                     fw.submit(os.path.join(gts_path, "%05d.png" % idx), surfel_path.quantize_u8(cam.original_image[0:3].to(dev)))
                     fw.submit(os.path.join(render_path, "%05d.png" % idx), surfel_path.quantize_u8(self.rgbmaps[idx]))
-                    fw.submit(os.path.join(vis_path, "depth_%05d.tiff" % idx), self.depthmaps[idx][0])
+                    if vis:
+                        fw.submit(os.path.join(vis_path, "depth_%05d.tiff" % idx), self.depthmaps[idx][0])
             return
         from PIL import Image
         for idx, cam in enumerate(self.viewpoint_stack):
@@ -462,6 +467,8 @@ def build_parser():
     ap.add_argument("--video_only", action="store_true", help="Path: write the videos and none of the per-frame files")
     ap.add_argument("--video_quality", default=95, type=int, help="Path: JPEG quality of the videos' frames, 1 .. 100")
     ap.add_argument("--fps", default=60, type=int, help="Path: frame rate of the videos")
+    ap.add_argument("--png", default="pillow", choices=["pillow", "device"], help="who encodes the PNG files of --render_path and of the renders / gt "
+                    "export: Pillow on host threads (the default) or the encoder on the device (PNG.md); the same names and pixels")
     return ap
 
 
@@ -470,6 +477,11 @@ def path_video_args(args):
     if not (args.video or args.video_only):
         return {}
     return dict(video=True, video_only=args.video_only, video_quality=args.video_quality, fps=args.fps)
+
+
+def path_png_args(args):
+    """render_path's and export_image's png argument from the CLI's: none at all unless the device encoder was asked for"""
+    return dict(png=args.png) if args.png != "pillow" else {}
 
 
 def main(argv=None):
@@ -495,12 +507,12 @@ def main(argv=None):
         for split, split_cams, skip in (("train", cams, args.skip_train), ("test", test_cams, args.skip_test)):
             if split_cams and not skip:
                 ext.reconstruction(split_cams)
-                ext.export_image(os.path.join(args.model_path, split, "ours_%d" % it))
+                ext.export_image(os.path.join(args.model_path, split, "ours_%d" % it), **path_png_args(args))
     if args.render_path:      # render.py:73-84, at the trained SH degree
         import surfel_path
         traj_dir = os.path.join(args.model_path, "traj", "ours_%d" % it)
         surfel_path.render_path(gaussians, cams, render, pipe, ext.background, traj_dir, n_frames=args.n_frames, vis_normals=args.vis_normals,
-                                **path_video_args(args))
+                                **path_video_args(args), **path_png_args(args))
         print("trajectory frames saved at {}".format(traj_dir))
     if args.skip_mesh:
         return 0

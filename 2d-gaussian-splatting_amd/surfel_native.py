@@ -188,6 +188,11 @@ SIGNATURES = {
         "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
         "surfel_jpeg_encode": (_i, _i, _i, _d, _i, _d, _i64, _d, _d, _i64, _s),
     },
+    "surfel_png.h": {
+        "surfel_png_capacity": (_i64, _i, _i, _i),
+        "surfel_png_scratch_bytes": (_i64, _i, _i, _i),
+        "surfel_png_encode": (_i, _i, _i, _i, _d, _d, _i64, _d, _d, _i64, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -200,6 +205,7 @@ VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
 VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
+PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

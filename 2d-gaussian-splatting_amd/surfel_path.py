@@ -228,9 +228,17 @@ class FrameWriter:
     (-> float32 TIFF with save_img_f32's values: NaN -> 0, +-inf -> +-FLT_MAX) on the device or the host, copies it into one of `ring`
     pinned host buffers without blocking, records an event behind the copy and hands the buffer to a pool of `workers` threads
     (at most 8) that wait for the event and encode with Pillow.  submit blocks only when all buffers are in flight: no more than
-    `ring` frames are ever retained.  close() waits for everything and re-raises the first exception a worker met."""
+    `ring` frames are ever retained.  close() waits for everything and re-raises the first exception a worker met.
+    png="device": a uint8 frame on the device is encoded there (surfel_png.encode_png, PNG.md) into one of `ring` device buffers and its
+    size word copied to pinned memory without blocking; the worker waits for the event, reads the size, copies exactly that many bytes
+    into the slot's pinned buffer on a side stream and writes them: only the compressed bytes cross.  Host tensors and the TIFFs stay
+    on Pillow.  png="pillow" (the default): every PNG through Pillow, as before."""
 
-    def __init__(self, workers=4, ring=None):
+    def __init__(self, workers=4, ring=None, png="pillow"):
+        if png not in ("pillow", "device"):
+            raise ValueError("FrameWriter: png must be 'pillow' or 'device', got %r" % (png,))
+        self.png = png
+        self._device = None                     # png="device": made by the first device PNG
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.ring = max(1, int(ring)) if ring is not None else 2 * self.workers
         self._pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="frame-writer")
@@ -276,6 +284,11 @@ class FrameWriter:
             slot = self._idle.pop()
         try:
             t = t.contiguous()
+            if kind == "PNG" and self.png == "device" and t.is_cuda:
+                event = self._encode_device(slot, t)
+                self.frames += 1
+                self._futures.append(self._pool.submit(self._write_device, slot, path, event))
+                return
             host = self._buffer(slot, t.numel() * t.element_size(), t.is_cuda).view(t.dtype).view(t.shape)
             event = None
             if t.is_cuda:
@@ -295,6 +308,51 @@ class FrameWriter:
         with self._lock:
             self._idle.append(slot)
         self._free.release()
+
+    def _encode_device(self, slot, t):
+        """the PNG file of a device frame into the slot's device buffer, its size into pinned memory; the event behind both"""
+        import surfel_png
+        d = self._device
+        if d is None:
+            with torch.cuda.device(t.device):
+                d = self._device = dict(device=t.device, stream=torch.cuda.Stream(device=t.device), buffers=[None] * self.ring,
+                                        sizes=torch.zeros(self.ring, dtype=torch.int64, device=t.device),
+                                        host_size=torch.zeros(self.ring, dtype=torch.int64).pin_memory())
+        elif d["device"] != t.device:
+            raise ValueError("FrameWriter(png='device'): frames of one writer must live on one device (%s, then %s)" % (d["device"], t.device))
+        cap = surfel_png.capacity(*t.shape)
+        with torch.cuda.device(t.device):
+            if d["buffers"][slot] is None or d["buffers"][slot].numel() < cap:
+                d["buffers"][slot] = torch.empty(cap, dtype=torch.uint8, device=t.device)
+            size = d["sizes"][slot:slot + 1]
+            surfel_png.encode_png(t, out=d["buffers"][slot], size=size)
+            d["host_size"][slot:slot + 1].copy_(size, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        return event
+
+    def _write_device(self, slot, path, event):
+        try:
+            d = self._device
+            event.synchronize()
+            n = int(d["host_size"][slot])
+            host = self._buffer(slot, n, True)
+            with torch.cuda.device(d["device"]), torch.cuda.stream(d["stream"]):
+                host.copy_(d["buffers"][slot][:n], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record()
+            done.synchronize()
+            self._store(path, memoryview(host.numpy()))
+        except BaseException as e:
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+        finally:
+            self._release(slot)
+
+    def _store(self, path, data):
+        with open(path, "wb") as f:
+            f.write(data)
 
     def _encode(self, slot, path, kind, host, event):
         try:
@@ -339,7 +397,7 @@ def _folders(out_dir, names):
 
 @torch.no_grad()
 def render_path(gaussians, cameras, render, pipe, background, out_dir, n_frames=240, vis_normals=False, workers=4, timings=None,
-                video=False, video_only=False, video_quality=95, fps=60):
+                video=False, video_only=False, video_quality=95, fps=60, png="pillow"):
     """render.py:73-84: the elliptical path through `cameras`, rendered frame by frame and written as
     out_dir/renders/%05d.png (colour), vis/depth_%05d.tiff (surf_depth, float32), video/depth/%05d.png (the depth video's frames:
     turbo of log depth between the 3rd and 97th percentile of frame 0) and, with vis_normals, vis/normal_%05d.png (rend_normal * 0.5 +
@@ -347,6 +405,7 @@ def render_path(gaussians, cameras, render, pipe, background, out_dir, n_frames=
     video: also out_dir/render_traj_color.avi, render_traj_depth.avi and, with vis_normals, render_traj_normal.avi (Motion-JPEG at
     video_quality and fps, VIDEO.md), fed from the very tensors that go to renders/, video/depth/ and vis/normal_*: create_videos'
     three videos, frame for frame, encoded on the device.  video_only: the videos and none of the per-frame files or folders.
+    png: "pillow" (the default) or "device": the PNG frames encoded on the device (FrameWriter(png=...), PNG.md); same names, same pixels.
     timings: a dict that receives the loop's host time and the writers' counters.  Returns the path cameras."""
     traj = generate_path(cameras, n_frames=n_frames)
     video = video or video_only
@@ -357,7 +416,7 @@ def render_path(gaussians, cameras, render, pipe, background, out_dir, n_frames=
         renders, vis, depth_dir = _folders(out_dir, ["renders", "vis", "video/depth"])
     lo = hi = None
     writers = {}
-    fw = None if video_only else FrameWriter(workers=workers)      # (video_only: no encoder threads, no pinned ring)
+    fw = None if video_only else FrameWriter(workers=workers, png=png)      # (video_only: no encoder threads, no pinned ring)
 
     def emit(name, frame, folder, pattern, idx):
         if fw is not None:
