@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsurfel_hip.so")
 SOURCES = ["surfel_preprocess.hip", "surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_sort.hip", "surfel_api.hip", "knn.hip", "box_probe.hip",
            "train_loss.hip", "train_post.hip", "train_fused.hip", "train_optim.hip", "train_api.hip",
-           "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "frame_jpeg.hip", "frame_png.hip"]
+           "device_scan.hip", "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "frame_jpeg.hip", "frame_png.hip"]
 # blend kernels: packed-f32 VALU (SLP) costs ~1.6x a scalar op on gfx950 plus the v_movs that pair the operands
 # surfel_backward.hip spells every fused multiply-add out (FMA macro) and is compiled with contraction off, so its kernel variants
 # round identically per (pixel, surfel) pair
@@ -40,7 +40,7 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          # restatement (tests/video_oracle.py) and the JPEG file comes out byte for byte
          "frame_jpeg.hip": ["-ffp-contract=off"]}
 HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
-           os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
+           os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", "mesh_mc.h", "block_ops.h", "side_util.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
            os.path.join("..", "..", "include", "surfel_mesh_unbounded.h"), os.path.join("..", "..", "include", "surfel_eval.h"),
            os.path.join("..", "..", "include", "surfel_eval_tnt.h"), os.path.join("..", "..", "include", "surfel_metrics.h"),
            os.path.join("..", "..", "include", "surfel_scene.h"), "vis_turbo_table.h", os.path.join("..", "..", "include", "surfel_vis.h"),

@@ -6,14 +6,10 @@
 #include <math.h>
 
 #include "../../include/surfel_eval.h"
-#include "surfel_kernels.h"
-#include "train_kernels.h"
+#include "block_ops.h"
+#include "side_util.h"
 
 namespace surfel {
-
-// mesh_tsdf.hip
-int64_t scan_scratch_u32(int64_t n);
-void scan_u32(uint32_t* a, int64_t n, uint32_t* scratch, hipStream_t st);
 
 constexpr int ET = 256;                    // threads per workgroup
 constexpr int EVAL_MEAN_BLOCKS = 1024;     // partial sums of eval_mean_kernel
@@ -275,34 +271,24 @@ __global__ void __launch_bounds__(ET) eval_fill_none_kernel(int64_t n, float* __
 }
 
 // ---- fixed-order means ----------------------------------------------------------------------------------------------------------
-__device__ inline void eval_block_sum(double& s, double& c, double* sh) {      // result in thread 0
-    sh[threadIdx.x] = s; sh[ET + threadIdx.x] = c;
-    __syncthreads();
-    for (int o = ET / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < (unsigned)o) { sh[threadIdx.x] += sh[threadIdx.x + o]; sh[ET + threadIdx.x] += sh[ET + threadIdx.x + o]; }
-        __syncthreads();
-    }
-    s = sh[0]; c = sh[ET];
-}
-
 // partial[2 b], partial[2 b + 1] = sum and count of the d < bound among the elements b * ET + t + k * (blocks * ET)
 __global__ void __launch_bounds__(ET) eval_mean_kernel(int64_t n, const float* __restrict__ d, float bound, double* __restrict__ partial) {
     __shared__ double sh[2 * ET];
-    double s = 0.0, c = 0.0;
+    double acc[2] = {0.0, 0.0};      // sum, count
     for (int64_t i = (int64_t)blockIdx.x * ET + threadIdx.x; i < n; i += (int64_t)gridDim.x * ET) {
         const float v = d[i];
-        if (v < bound) { s += (double)v; c += 1.0; }
+        if (v < bound) { acc[0] += (double)v; acc[1] += 1.0; }
     }
-    eval_block_sum(s, c, sh);
-    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s; partial[2 * blockIdx.x + 1] = c; }
+    block_tree_sum<ET>(acc, sh);
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = sh[0]; partial[2 * blockIdx.x + 1] = sh[ET]; }
 }
 
 __global__ void __launch_bounds__(ET) eval_mean_top_kernel(int nb, const double* __restrict__ partial, double* __restrict__ out) {
     __shared__ double sh[2 * ET];
-    double s = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < nb; i += ET) { s += partial[2 * i]; c += partial[2 * i + 1]; }
-    eval_block_sum(s, c, sh);
-    if (threadIdx.x == 0) { out[0] = s; out[1] = c; }
+    double acc[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < nb; i += ET) { acc[0] += partial[2 * i]; acc[1] += partial[2 * i + 1]; }
+    block_tree_sum<ET>(acc, sh);
+    if (threadIdx.x == 0) { out[0] = sh[0]; out[1] = sh[ET]; }
 }
 
 // ---- rule 7: dilation and culling -------------------------------------------------------------------------------------------------
@@ -364,13 +350,7 @@ __global__ void __launch_bounds__(ET) eval_cull_kernel(int64_t n, const float* _
 using namespace surfel;
 
 namespace {
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-inline unsigned grid(int64_t n) { return (unsigned)((n + ET - 1) / ET); }
-template <class T>
-T* take(surfel_alloc_fn alloc, void* user, int64_t n) { return static_cast<T*>(alloc(user, (size_t)(n > 0 ? n : 1) * sizeof(T))); }
+inline unsigned grid(int64_t n) { return blocks_for(n, ET); }
 inline int64_t cells_of(const surfel_eval_grid* g) { return (int64_t)g->dims[0] * g->dims[1] * g->dims[2]; }
 inline bool grid_fields_ok(const surfel_eval_grid* g) {
     return g && g->dims[0] > 0 && g->dims[1] > 0 && g->dims[2] > 0 && g->cell > 0.f && g->cell < INFINITY && cells_of(g) < ((int64_t)1 << 31) &&

@@ -6,14 +6,10 @@
 #include <math.h>
 
 #include "../../include/surfel_eval_tnt.h"
-#include "surfel_kernels.h"
-#include "train_kernels.h"
+#include "block_ops.h"
+#include "side_util.h"
 
 namespace surfel {
-
-// mesh_tsdf.hip
-int64_t scan_scratch_u32(int64_t n);
-void scan_u32(uint32_t* a, int64_t n, uint32_t* scratch, hipStream_t st);
 
 constexpr int TT = 256;                    // threads per workgroup
 constexpr int TNT_SUM_BLOCKS = 1024;       // partial sums of tnt_corr_sums_kernel
@@ -144,24 +140,11 @@ __global__ void __launch_bounds__(TT) tnt_voxel_mean_kernel(int64_t n, const flo
 }
 
 // ---- rule 5: the correspondence sums ---------------------------------------------------------------------------------------------------
-// acc[0..17] of every thread -> their sums in sh[k * TT] (k = 0..17), by a tree of fixed shape
-#define TNT_FOR_SUMS(k) _Pragma("unroll") for (int k = 0; k < NS; k++)
-
-__device__ inline void tnt_block_sums(const double (&acc)[NS], double* sh) {
-    TNT_FOR_SUMS(k) sh[k * TT + threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int o = TT / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < (unsigned)o) TNT_FOR_SUMS(k) sh[k * TT + threadIdx.x] += sh[k * TT + threadIdx.x + o];
-        __syncthreads();
-    }
-}
-
 // partial[NS b + k] = the k-th sum over the elements b * TT + t + j * (blocks * TT)
 __global__ void __launch_bounds__(TT) tnt_corr_sums_kernel(int64_t n, const float* __restrict__ source, const int32_t* __restrict__ index, int64_t nt,
                                                            const float* __restrict__ target, double* __restrict__ partial) {
     __shared__ double sh[NS * TT];
-    double acc[NS];
-    TNT_FOR_SUMS(k) acc[k] = 0.0;
+    double acc[NS] = {};
     for (int64_t i = (int64_t)blockIdx.x * TT + threadIdx.x; i < n; i += (int64_t)gridDim.x * TT) {
         const int64_t j = index[i];
         if (j < 0 || j >= nt) continue;
@@ -177,16 +160,18 @@ __global__ void __launch_bounds__(TT) tnt_corr_sums_kernel(int64_t n, const floa
         acc[16] += (x0 * x0 + x1 * x1) + x2 * x2;
         acc[17] += (d0 * d0 + d1 * d1) + d2 * d2;
     }
-    tnt_block_sums(acc, sh);
+    block_tree_sum<TT>(acc, sh);      // sums in sh[k * TT]
     if (threadIdx.x < NS) partial[NS * blockIdx.x + threadIdx.x] = sh[threadIdx.x * TT];
 }
 
 __global__ void __launch_bounds__(TT) tnt_corr_sums_top_kernel(int nb, const double* __restrict__ partial, double* __restrict__ out) {
     __shared__ double sh[NS * TT];
-    double acc[NS];
-    TNT_FOR_SUMS(k) acc[k] = 0.0;
-    for (int i = threadIdx.x; i < nb; i += TT) TNT_FOR_SUMS(k) acc[k] += partial[NS * i + k];
-    tnt_block_sums(acc, sh);
+    double acc[NS] = {};
+    for (int i = threadIdx.x; i < nb; i += TT) {
+#pragma unroll
+        for (int k = 0; k < NS; k++) acc[k] += partial[NS * i + k];
+    }
+    block_tree_sum<TT>(acc, sh);      // sums in sh[k * TT]
     if (threadIdx.x < NS) out[threadIdx.x] = sh[threadIdx.x * TT];
 }
 
@@ -224,13 +209,7 @@ __global__ void __launch_bounds__(TT) tnt_hist_kernel(int64_t n, const float* __
 using namespace surfel;
 
 namespace {
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-inline unsigned grid(int64_t n) { return (unsigned)((n + TT - 1) / TT); }
-template <class T>
-T* take(surfel_alloc_fn alloc, void* user, int64_t n) { return static_cast<T*>(alloc(user, (size_t)(n > 0 ? n : 1) * sizeof(T))); }
+inline unsigned grid(int64_t n) { return blocks_for(n, TT); }
 constexpr int64_t TNT_MAX_POINTS = ((int64_t)1 << 31) - 1;
 }  // namespace
 
@@ -290,13 +269,10 @@ int64_t surfel_tnt_voxel_down_sample(surfel_alloc_fn alloc, void* user, int64_t 
     const TVox v{origin[0], origin[1], origin[2], voxel};
     hipLaunchKernelGGL(tnt_voxel_keys_kernel, dim3(grid(n)), dim3(TT), 0, st, n, points, v, lo, hi, ka, va, flag);
     // the 63-bit key as two stable LSD sorts of its 32-bit halves: low word first, then high word
-    int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, 32, scratch, st);
-    if (r < 0) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
-    uint32_t* k1 = r ? kb : ka; uint32_t* v1 = r ? vb : va; uint32_t* k2 = r ? ka : kb; uint32_t* v2 = r ? va : vb;
-    hipLaunchKernelGGL(tnt_voxel_hi_kernel, dim3(grid(n)), dim3(TT), 0, st, n, hi, v1, k1);
-    r = radix_sort_pairs_u32(k1, v1, k2, v2, (size_t)n, 0, 3 * AXIS_BITS - 32, scratch, st);
-    if (r < 0) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
-    const uint32_t* perm = r ? v2 : v1;
+    const uint32_t* perm = sort_pairs_two_words(ka, va, kb, vb, n, 32, 3 * AXIS_BITS - 32, scratch, st, [&](const uint32_t* val, uint32_t* key) {
+        hipLaunchKernelGGL(tnt_voxel_hi_kernel, dim3(grid(n)), dim3(TT), 0, st, n, hi, val, key);
+    });
+    if (!perm) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
     hipLaunchKernelGGL(tnt_voxel_heads_kernel, dim3(grid(n + 1)), dim3(TT), 0, st, n, lo, hi, perm, head);
     scan_u32(head, n + 1, sums, st);
     uint32_t host[2] = {0, 0};      // cell count, flag

@@ -22,8 +22,9 @@
 #include <initializer_list>
 
 #include "../../include/surfel_jpeg.h"
+#include "block_ops.h"
 #include "jpeg_tables.h"
-#include "train_kernels.h"
+#include "side_util.h"
 
 namespace surfel {
 
@@ -101,33 +102,6 @@ __global__ void __launch_bounds__(JT_MCU) jpeg_transform_kernel(int H, int W, in
 }
 
 // ---- entropy coding ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
-// exclusive scan of v over the workgroup (JT threads); total = the sum.  s_w: JT / 64 words of LDS
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan(v, lane);
-    __syncthreads();                         // (the previous round's reads of s_w are done)
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < JT / 64; k++) {
-        const uint32_t c = s_w[k];
-        if (k < wv) before += c;
-        sum += c;
-    }
-    *total = sum;
-    return before + incl - v;
-}
-
 __device__ __forceinline__ int category(int v) {      // number of bits of |v|
     const int a = v < 0 ? -v : v;
     return a ? 32 - __clz(a) : 0;
@@ -184,7 +158,7 @@ __global__ void __launch_bounds__(JT) jpeg_block_bits_kernel(int64_t nblocks, in
     uint64_t bits;
     int len;
     lane_code(coef, blk, mcus, lane, &bits, &len);
-    const uint32_t total = wave_incl_scan((uint32_t)len, lane);
+    const uint32_t total = wave_incl_sum((uint32_t)len);
     if (lane == 63) blockbits[blk] = total;
 }
 
@@ -199,7 +173,7 @@ __global__ void __launch_bounds__(JT) jpeg_row_scan_kernel(int mcus, uint32_t* _
         const int i = i0 + threadIdx.x;
         const uint32_t v = i < n ? bb[i] : 0u;
         uint32_t total;
-        const uint32_t ex = block_excl_scan(v, s_w, &total);
+        const uint32_t ex = block_excl_sum<JT>(v, s_w, &total);
         if (i < n) bb[i] = carry + ex;
         carry += total;
     }
@@ -228,7 +202,7 @@ __global__ void __launch_bounds__(JT) jpeg_emit_kernel(int64_t nblocks, int mcus
         int len;
         lane_code(coef, blk, mcus, lane, &bits, &len);
         start = blockoff[blk];
-        const uint32_t incl = wave_incl_scan((uint32_t)len, lane);      // (all 64 lanes)
+        const uint32_t incl = wave_incl_sum((uint32_t)len);      // (all 64 lanes)
         if (len > 0) {
             const uint32_t o = (start & 31u) + incl - (uint32_t)len;
             const uint64_t x = bits << (64 - len);      // left-aligned
@@ -263,7 +237,7 @@ __global__ void __launch_bounds__(JT) jpeg_count_kernel(RowInfo* __restrict__ ro
     uint32_t c = 0;
     for (int64_t i = threadIdx.x; i < nwords; i += JT) c += count_ff(src[i], i * 4, nbytes);
     uint32_t total;
-    block_excl_scan(c, s_w, &total);
+    block_excl_sum<JT>(c, s_w, &total);
     if (threadIdx.x == 0) rows[blockIdx.x].nff = total;
 }
 
@@ -275,7 +249,7 @@ __global__ void __launch_bounds__(JT) jpeg_finish_kernel(int nrows, RowInfo* __r
         uint32_t v = 0;
         if (r < nrows) v = ((rows[r].bits + 7u) >> 3) + rows[r].nff + (r < nrows - 1 ? 2u : 0u);
         uint32_t total;
-        const uint32_t ex = block_excl_scan(v, s_w, &total);
+        const uint32_t ex = block_excl_sum<JT>(v, s_w, &total);
         if (r < nrows) rows[r].off = carry + ex;
         carry += total;
     }
@@ -299,7 +273,7 @@ __global__ void __launch_bounds__(JT) jpeg_stuff_kernel(int nrows, const RowInfo
         const int64_t i = i0 + threadIdx.x;
         const uint32_t word = i < nwords ? src[i] : 0u;
         uint32_t total;
-        const uint32_t ex = block_excl_scan(i < nwords ? count_ff(word, i * 4, nbytes) : 0u, s_w, &total);
+        const uint32_t ex = block_excl_sum<JT>(i < nwords ? count_ff(word, i * 4, nbytes) : 0u, s_w, &total);
         int64_t p = i * 4 + carry + ex;
         if (i < nwords) {
 #pragma unroll
@@ -383,11 +357,6 @@ inline int jpeg_header(int H, int W, int mcus, const JpegQuant& qt, JpegHeader* 
     return (int)(p - hdr->b);
 }
 
-inline int jpeg_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-
 }  // namespace
 }  // namespace surfel
 
@@ -436,7 +405,7 @@ int surfel_jpeg_encode(int H, int W, const uint8_t* rgb, int quality, uint8_t* d
     hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, rows, rowbuf, row_words);
     hipLaunchKernelGGL(jpeg_finish_kernel, dim3(1), dim3(JT), 0, s, (int)g.rows, rows, hdr, dst, size);
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, (int)g.rows, rows, rowbuf, row_words, dst + SURFEL_JPEG_HEADER_BYTES);
-    return jpeg_launched("jpeg_encode kernels");
+    return launched("jpeg_encode kernels");
 }
 
 }  // extern "C"

@@ -20,7 +20,8 @@
 #include <string.h>
 
 #include "../../include/surfel_png.h"
-#include "train_kernels.h"
+#include "block_ops.h"
+#include "side_util.h"
 
 namespace surfel {
 
@@ -57,106 +58,6 @@ struct PngShape {
     int stripes;
     int64_t cap_full;    // bytes of the bit buffer of a full stripe
 };
-
-// ---- scans and reductions over a workgroup of NT threads ---------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ uint32_t block_scan_max(uint32_t v, uint32_t* s_w) {      // inclusive, towards higher threads
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v = max(v, o);
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wv] = v;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NT / 64; k++)
-        if (k < wv) v = max(v, s_w[k]);
-    return v;
-}
-
-template <int NT>
-__device__ __forceinline__ uint32_t block_scan_min_suffix(uint32_t v, uint32_t* s_w) {      // inclusive, towards lower threads
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_down(v, off, 64);
-        if (lane + off < 64) v = min(v, o);
-    }
-    __syncthreads();
-    if (lane == 0) s_w[wv] = v;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NT / 64; k++)
-        if (k > wv) v = min(v, s_w[k]);
-    return v;
-}
-
-template <int NT>
-__device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t* s_w) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor(v, off, 64));
-    __syncthreads();
-    if (lane == 0) s_w[wv] = v;
-    __syncthreads();
-    uint32_t r = s_w[0];
-#pragma unroll
-    for (int k = 1; k < NT / 64; k++) r = min(r, s_w[k]);
-    return r;
-}
-
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* s_w, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; k++) {
-        const uint32_t c = s_w[k];
-        if (k < wv) before += c;
-        sum += c;
-    }
-    *total = sum;
-    return before + incl - v;
-}
-
-template <int NT>
-__device__ __forceinline__ uint64_t block_sum64(uint64_t v, uint64_t* s_w) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
-    __syncthreads();
-    if (lane == 0) s_w[wv] = v;
-    __syncthreads();
-    uint64_t r = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; k++) r += s_w[k];
-    return r;
-}
-
-template <int NT>
-__device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t* s_w) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v ^= (uint32_t)__shfl_xor(v, off, 64);
-    __syncthreads();
-    if (lane == 0) s_w[wv] = v;
-    __syncthreads();
-    uint32_t r = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; k++) r ^= s_w[k];
-    return r;
-}
 
 // ---- filter --------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int paeth(int a, int b, int c) {
@@ -708,11 +609,6 @@ inline void put_be32(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
 }
 
-inline int png_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-
 }  // namespace
 }  // namespace surfel
 
@@ -770,7 +666,7 @@ int surfel_png_encode(int H, int W, int C, const uint8_t* pix, uint8_t* dst, int
     hipLaunchKernelGGL(png_layout_kernel, dim3(1), dim3(PF), 0, s, g.sh, rowsum, info, meta);
     hipLaunchKernelGGL(png_compact_kernel, dim3(S), dim3(PF), 0, s, g.sh, info, bitbuf, dst + SURFEL_PNG_FRONT_BYTES);
     hipLaunchKernelGGL(png_finish_kernel, dim3(1), dim3(PF), 0, s, g.sh, info, meta, front, head_crc, dst, size);
-    return png_launched("png_encode kernels");
+    return launched("png_encode kernels");
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 #include <math.h>
 
 #include "../../include/surfel_vis.h"
-#include "train_kernels.h"
+#include "side_util.h"
 #include "vis_pixels.h"
 #include "vis_turbo_table.h"
 
@@ -205,14 +205,9 @@ __global__ void __launch_bounds__(VT) vis_order_narrow_kernel(uint32_t* __restri
 
 namespace {
 
-inline int vis_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-
 constexpr int VIS_MAX_EDGE = 65536;
 
-inline unsigned pixel_blocks(int64_t hw) { return (unsigned)((hw + (int64_t)VT * PX - 1) / ((int64_t)VT * PX)); }
+inline unsigned pixel_blocks(int64_t hw) { return blocks_for(hw, (int64_t)VT * PX); }
 
 }  // namespace
 }  // namespace surfel
@@ -229,7 +224,7 @@ int surfel_vis_quantize(int C, int H, int W, const float* planes, float scale, f
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (C == 1) hipLaunchKernelGGL(vis_quantize_kernel<1>, dim3(pixel_blocks(hw)), dim3(VT), 0, s, hw, planes, scale, bias, dst);
     else hipLaunchKernelGGL(vis_quantize_kernel<3>, dim3(pixel_blocks(hw)), dim3(VT), 0, s, hw, planes, scale, bias, dst);
-    return vis_launched("vis_quantize_kernel");
+    return launched("vis_quantize_kernel");
 }
 
 int surfel_vis_order_stats(int64_t n, const float* x, int m, const int64_t* ranks, float* out, void* scratch, int64_t scratch_bytes,
@@ -255,7 +250,7 @@ int surfel_vis_order_stats(int64_t n, const float* x, int m, const int64_t* rank
         hipLaunchKernelGGL(vis_order_hist_kernel, dim3(blocks), dim3(VT), 0, s, n, x, shift, hist, st);
         hipLaunchKernelGGL(vis_order_narrow_kernel, dim3(1), dim3(VT), 0, s, hist, st, m, shift == 0 ? 1 : 0, out);
     }
-    return vis_launched("vis_order_stats kernels");
+    return launched("vis_order_stats kernels");
 }
 
 int surfel_vis_depth_turbo(int H, int W, const float* depth, double lo, double hi, uint8_t* dst, void* stream) {
@@ -265,7 +260,7 @@ int surfel_vis_depth_turbo(int H, int W, const float* depth, double lo, double h
     // (a NaN limit makes the range NaN, and with it every t)
     hipLaunchKernelGGL(vis_depth_turbo_kernel, dim3(pixel_blocks(hw)), dim3(VT), 0, static_cast<hipStream_t>(stream), hw, depth, lo < hi ? lo : hi,
                        fabs(hi - lo), dst);
-    return vis_launched("vis_depth_turbo_kernel");
+    return launched("vis_depth_turbo_kernel");
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 #include <math.h>
 
 #include "../../include/surfel_cull.h"
-#include "train_kernels.h"
+#include "side_util.h"
 
 namespace surfel {
 
@@ -193,11 +193,7 @@ __global__ void __launch_bounds__(CT) cull_visibility_kernel(int64_t N, const fl
 }
 
 namespace {
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-inline unsigned grid(int64_t n) { return (unsigned)((n + CT - 1) / CT); }
+inline unsigned grid(int64_t n) { return blocks_for(n, CT); }
 constexpr int64_t CULL_MAX_ELEMS = ((int64_t)1 << 31) - 1;
 
 bool bad_cameras(int nviews, const float* w2c, const float* intrinsics, int n_intrinsics) {

@@ -4,16 +4,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/surfel_mesh.h"
-#include "mesh_mc_table.h"
-#include "surfel_kernels.h"
-#include "train_kernels.h"
+#include "mesh_mc.h"
+#include "side_util.h"
 
 namespace surfel {
 
 constexpr int MB = SURFEL_TSDF_BLOCK;            // voxels per block edge
 constexpr int MV = MB * MB * MB;                 // voxels per block (4096)
 constexpr int MT = 256;                          // threads per workgroup: 16 voxels per thread
-constexpr int SCAN_TILE = MT * 16;               // elements per scan tile
 // V and F index with int32 and every voxel emits at most 3 vertices and MC_MAX_TRI triangles
 constexpr int64_t MAX_BLOCKS = ((int64_t)1 << 31) / ((int64_t)MV * MC_MAX_TRI);
 
@@ -269,77 +267,11 @@ __global__ void __launch_bounds__(MT) mesh_emit_kernel(Vol v, const int32_t* __r
             }
         }
         if (!(code >> 8 & 1u)) continue;
-        const uint32_t cs = code & 255u, nt = MC_NTRI[cs];
-        const uint32_t t0 = tbase[me];
-        for (uint32_t t = 0; t < nt; t++)
-            for (int j = 0; j < 3; j++) {
-                const uint8_t* e = MC_EDGE[MC_TRIS[cs][3 * t + j]];
-                const int64_t o = voxel_at(v, x + e[0], y + e[1], gz + e[2]);      // the edge's owner: allocated, the cube is valid
-                const uint32_t om = info[o] >> 9 & ((1u << e[3]) - 1u);
-                tris[3 * ((size_t)t0 + t) + j] = (int32_t)(vbase[o] + __popc(om));
-            }
+        mc_write_triangles(code & 255u, tris + 3 * (size_t)tbase[me], [&](const uint8_t* e) {
+            const int64_t o = voxel_at(v, x + e[0], y + e[1], gz + e[2]);      // the edge's owner: allocated, the cube is valid
+            return vbase[o] + __popc(info[o] >> 9 & ((1u << e[3]) - 1u));
+        });
     }
-}
-
-// ---- exclusive scan of u32 (in place), three launches: tile sums, one-workgroup scan of the sums, tile scans ------------
-__device__ uint32_t block_exclusive_scan(uint32_t x, uint32_t* sh) {      // returns the workgroup total in sh[MT]
-    sh[threadIdx.x] = x;
-    __syncthreads();
-    for (int o = 1; o < MT; o <<= 1) {
-        const uint32_t y = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += y;
-        __syncthreads();
-    }
-    const uint32_t incl = sh[threadIdx.x];
-    if (threadIdx.x == MT - 1) sh[MT] = incl;
-    __syncthreads();
-    return incl - x;
-}
-
-// scans elements [base, base + SCAN_TILE) of a (thread t: 16 consecutive) adding `carry`; returns the tile total
-__device__ uint32_t scan_tile(uint32_t* a, int64_t n, int64_t base, uint32_t carry, uint32_t* sh) {
-    uint32_t v[16], sum = 0;
-    const int64_t b = base + 16 * (int64_t)threadIdx.x;
-    for (int i = 0; i < 16; i++) { v[i] = b + i < n ? a[b + i] : 0u; sum += v[i]; }
-    uint32_t run = block_exclusive_scan(sum, sh) + carry;
-    const uint32_t total = sh[MT];
-    __syncthreads();
-    for (int i = 0; i < 16; i++)
-        if (b + i < n) { a[b + i] = run; run += v[i]; }
-    return total;
-}
-
-__global__ void __launch_bounds__(MT) scan_sums_kernel(const uint32_t* __restrict__ a, int64_t n, uint32_t* __restrict__ sums) {
-    __shared__ uint32_t sh[MT + 1];
-    const int64_t b = (int64_t)blockIdx.x * SCAN_TILE + 16 * (int64_t)threadIdx.x;
-    uint32_t sum = 0;
-    for (int i = 0; i < 16; i++) sum += b + i < n ? a[b + i] : 0u;
-    block_exclusive_scan(sum, sh);
-    if (threadIdx.x == 0) sums[blockIdx.x] = sh[MT];
-}
-
-__global__ void __launch_bounds__(MT) scan_top_kernel(uint32_t* __restrict__ sums, int64_t ntiles) {      // sums[ntiles] = total
-    __shared__ uint32_t sh[MT + 1];
-    uint32_t carry = 0;
-    for (int64_t base = 0; base < ntiles; base += SCAN_TILE) carry += scan_tile(sums, ntiles, base, carry, sh);
-    if (threadIdx.x == 0) sums[ntiles] = carry;
-}
-
-__global__ void __launch_bounds__(MT) scan_apply_kernel(uint32_t* __restrict__ a, int64_t n, const uint32_t* __restrict__ sums) {
-    __shared__ uint32_t sh[MT + 1];
-    scan_tile(a, n, (int64_t)blockIdx.x * SCAN_TILE, sums[blockIdx.x], sh);
-}
-
-int64_t scan_scratch_u32(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE + 1; }
-
-// exclusive scan of a[n] in place; the total lands in scratch[ntiles] (device)
-void scan_u32(uint32_t* a, int64_t n, uint32_t* scratch, hipStream_t st) {
-    const int64_t nt = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (nt == 0) { (void)hipMemsetAsync(scratch, 0, 4, st); return; }
-    hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)nt), dim3(MT), 0, st, a, n, scratch);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(MT), 0, st, scratch, nt);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nt), dim3(MT), 0, st, a, n, scratch);
 }
 
 // ---- connected components over shared edges -------------------------------------------------------------------------------
@@ -457,17 +389,11 @@ __global__ void __launch_bounds__(MT) copy_flags_kernel(int64_t n, const uint32_
 using namespace surfel;
 
 namespace {
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-inline unsigned grid(int64_t n) { return (unsigned)((n + MT - 1) / MT); }
+inline unsigned grid(int64_t n) { return blocks_for(n, MT); }
 inline int64_t table_n(const surfel_tsdf_volume* v) { return (int64_t)v->dims[0] * v->dims[1] * v->dims[2]; }
 inline Vol vol_of(const surfel_tsdf_volume* v) {
     return Vol{v->origin[0], v->origin[1], v->origin[2], v->dims[0], v->dims[1], v->dims[2], v->voxel_size, v->sdf_trunc, v->table};
 }
-template <class T>
-T* take(surfel_alloc_fn alloc, void* user, int64_t n) { return static_cast<T*>(alloc(user, (size_t)(n > 0 ? n : 1) * sizeof(T))); }
 }  // namespace
 
 extern "C" {
@@ -610,13 +536,10 @@ int surfel_mesh_clusters(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F
     if (!ka || !va || !kb || !vb || !parent || !scratch) return api_fail(SURFEL_E_ALLOC, "mesh_clusters: allocator returned NULL");
     // (min, max) keys as two stable LSD sorts of 32-bit halves: max first, then min
     hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, (uint32_t)V, tris, ka, va);
-    int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, bits, scratch, st);
-    if (r < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
-    uint32_t* k1 = r ? kb : ka; uint32_t* v1 = r ? vb : va; uint32_t* k2 = r ? ka : kb; uint32_t* v2 = r ? va : vb;
-    hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, v1, k1);
-    r = radix_sort_pairs_u32(k1, v1, k2, v2, (size_t)n, 0, bits, scratch, st);
-    if (r < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
-    const uint32_t* vs = r ? v2 : v1;
+    const uint32_t* vs = sort_pairs_two_words(ka, va, kb, vb, n, bits, bits, scratch, st, [&](const uint32_t* val, uint32_t* key) {
+        hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, val, key);
+    });
+    if (!vs) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
     hipLaunchKernelGGL(uf_init_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, size);
     hipLaunchKernelGGL(uf_hook_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, vs, parent);
     hipLaunchKernelGGL(uf_jump_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, label);

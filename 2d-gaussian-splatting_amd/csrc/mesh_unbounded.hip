@@ -1,22 +1,17 @@
 // mesh_unbounded.hip — unbounded mesh extraction: TSDF fusion on a contracted lattice, marching cubes over z-slabs and vertex colours
 // (include/surfel_mesh_unbounded.h, MESH.md §Unbounded).  Every output is written by exactly one thread and read back in a fixed
-// order: no atomics, so the result does not depend on launch order.  The exclusive scan and the case table are mesh_tsdf.hip's.
+// order: no atomics, so the result does not depend on launch order.  The exclusive scan is device_scan.hip's; the case table and the
+// triangle writer (mesh_mc.h) are shared with mesh_tsdf.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "../../include/surfel_mesh_unbounded.h"
-#include "mesh_mc_table.h"
-#include "surfel_kernels.h"
-#include "train_kernels.h"
+#include "mesh_mc.h"
+#include "side_util.h"
 
 namespace surfel {
-
-// mesh_tsdf.hip: exclusive scan of u32 in place, three launches; scratch words for n elements
-int64_t scan_scratch_u32(int64_t n);
-void scan_u32(uint32_t* a, int64_t n, uint32_t* scratch, hipStream_t st);
-
 namespace {
 
 constexpr int UT = 256;                      // threads per workgroup
@@ -169,15 +164,10 @@ __global__ void __launch_bounds__(UT) unb_emit_kernel(Lat L, int z0, int z1, int
         }
     }
     if (!(code >> 11 & 1u)) return;
-    const uint32_t cs = code & 255u, nt = MC_NTRI[cs];
-    const int64_t t0 = tb + tbase[k];
-    for (uint32_t t = 0; t < nt; t++)
-        for (int j = 0; j < 3; j++) {
-            const uint8_t* e = MC_EDGE[MC_TRIS[cs][3 * t + j]];
-            const int64_t o = k + e[0] + M * e[1] + M2 * e[2];      // the edge's owner (plane l + 1 <= z1 - z0 is in the scratch)
-            const uint32_t om = info[o] >> 8 & ((1u << e[3]) - 1u);
-            tris[3 * (t0 + t) + j] = (int32_t)(vb + vbase[o] + __popc(om));
-        }
+    mc_write_triangles(code & 255u, tris + 3 * (tb + tbase[k]), [&](const uint8_t* e) {
+        const int64_t o = k + e[0] + M * e[1] + M2 * e[2];      // the edge's owner (plane l + 1 <= z1 - z0 is in the scratch)
+        return vb + vbase[o] + __popc(info[o] >> 8 & ((1u << e[3]) - 1u));
+    });
 }
 
 // ---- vertex colours ---------------------------------------------------------------------------------------------------------------
@@ -204,13 +194,7 @@ __global__ void __launch_bounds__(UT) unb_color_kernel(int64_t V, const float* _
     colors[3 * i] = r * inv; colors[3 * i + 1] = g * inv; colors[3 * i + 2] = b * inv;
 }
 
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-inline unsigned grid(int64_t n) { return (unsigned)((n + UT - 1) / UT); }
-template <class T>
-T* take(surfel_alloc_fn alloc, void* user, int64_t n) { return static_cast<T*>(alloc(user, (size_t)(n > 0 ? n : 1) * sizeof(T))); }
+inline unsigned grid(int64_t n) { return blocks_for(n, UT); }
 
 inline Lat lat_of(const surfel_unbounded_volume* v) {
     return Lat{v->M, v->R, 2.f * v->R / (float)(v->M - 1), v->center[0], v->center[1], v->center[2], v->radius, v->voxel_size};

@@ -6,7 +6,8 @@
 #include <math.h>
 
 #include "../../include/surfel_metrics.h"
-#include "train_kernels.h"
+#include "block_ops.h"
+#include "side_util.h"
 
 namespace surfel {
 
@@ -134,17 +135,6 @@ __global__ void __launch_bounds__(MT) lpips_pool_kernel(int H, int W, int C4, co
     out[i] = max4(max4(in[a], in[a + C4]), max4(in[a + row], in[a + row + C4]));
 }
 
-// ---- block sum in a fixed order -------------------------------------------------------------------------------------------------------
-__device__ inline float block_sum(float v, float* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = MT / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < (unsigned)o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 // ---- the LPIPS tap ---------------------------------------------------------------------------------------------------------------------
 // G = min(64, C / 4) lanes share a pixel, each holding up to two float4 of either image's features.
 __global__ void __launch_bounds__(MT) lpips_tap_kernel(int64_t hw, int C, const float* __restrict__ feat, const float* __restrict__ lin,
@@ -159,7 +149,7 @@ __global__ void __launch_bounds__(MT) lpips_tap_kernel(int64_t hw, int C, const 
         const int c4 = sub + j * G;
         w[j] = 4 * c4 < C ? reinterpret_cast<const float4*>(lin)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float acc = 0.f;
+    float acc[1] = {0.f};
     // (every lane of a wave runs the same number of iterations: the shuffles below need them all; a pixel past the end reads nothing)
     for (int64_t p0 = (int64_t)blockIdx.x * per_block; p0 < hw; p0 += (int64_t)gridDim.x * per_block) {
         const int64_t p = p0 + slot;
@@ -189,22 +179,22 @@ __global__ void __launch_bounds__(MT) lpips_tap_kernel(int64_t hw, int C, const 
             s += (w[j].x * (d0 * d0) + w[j].y * (d1 * d1)) + (w[j].z * (d2 * d2) + w[j].w * (d3 * d3));
         }
         for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (sub == 0) acc += s;
+        if (sub == 0) acc[0] += s;
     }
-    const float total = block_sum(acc, sh);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+    block_tree_sum<MT>(acc, sh);      // in a fixed order
+    if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
 }
 
 // ---- squared error ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MT) sq_err_kernel(int64_t n, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ partials) {
     __shared__ float sh[MT];
-    float acc = 0.f;
+    float acc[1] = {0.f};
     for (int64_t i = (int64_t)blockIdx.x * MT + threadIdx.x; i < n; i += (int64_t)gridDim.x * MT) {
         const float d = a[i] - b[i];
-        acc += d * d;
+        acc[0] += d * d;
     }
-    const float total = block_sum(acc, sh);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+    block_tree_sum<MT>(acc, sh);      // in a fixed order
+    if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
 }
 
 }  // namespace surfel
@@ -213,10 +203,6 @@ __global__ void __launch_bounds__(MT) sq_err_kernel(int64_t n, const float* __re
 using namespace surfel;
 
 namespace {
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
 inline bool bad_size(int H, int W) { return H <= 0 || W <= 0; }
 inline bool too_large(int H, int W) { return H > SURFEL_LPIPS_MAX_EDGE || W > SURFEL_LPIPS_MAX_EDGE; }
 }  // namespace

@@ -7,7 +7,7 @@
 #include <math.h>
 
 #include "../../include/surfel_scene.h"
-#include "train_kernels.h"
+#include "side_util.h"
 
 namespace surfel {
 
@@ -143,11 +143,6 @@ __global__ void __launch_bounds__(ST) composite_kernel(int64_t hw, double bg, co
 }
 
 namespace {
-
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
 
 inline bool bad_edge(int v) { return v <= 0; }
 inline bool big_edge(int v) { return v > SURFEL_SCENE_MAX_EDGE; }

@@ -6,16 +6,9 @@
 
 #include "../../include/surfel_debug.h"
 #include "../../include/surfel_train.h"
-#include "train_kernels.h"
+#include "side_util.h"
 
 using namespace surfel;
-
-namespace {
-inline int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-}  // namespace
 
 extern "C" {
 

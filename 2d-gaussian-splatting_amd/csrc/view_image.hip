@@ -9,7 +9,7 @@
 #include <string>
 
 #include "../../include/surfel_view.h"
-#include "train_kernels.h"
+#include "side_util.h"
 #include "vis_pixels.h"
 #include "vis_turbo_table.h"
 
@@ -152,12 +152,7 @@ inline int view_check(const char* who, int H, int W, const void* src, const void
     return 0;
 }
 
-inline int view_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_fail(SURFEL_E_HIP, what, e);
-}
-
-inline unsigned view_blocks(int64_t hw) { return (unsigned)((hw + (int64_t)VW_T * PX - 1) / ((int64_t)VW_T * PX)); }
+inline unsigned view_blocks(int64_t hw) { return blocks_for(hw, (int64_t)VW_T * PX); }
 
 }  // namespace
 }  // namespace surfel
@@ -174,7 +169,7 @@ int surfel_view_scalar(int H, int W, const float* map, uint8_t* dst, void* scrat
     hipLaunchKernelGGL(view_reset_kernel, dim3(1), dim3(64), 0, s, keys);
     hipLaunchKernelGGL(view_minmax_kernel, dim3(view_blocks(hw)), dim3(VW_T), 0, s, hw, map, keys);
     hipLaunchKernelGGL(view_colour_kernel, dim3(view_blocks(hw)), dim3(VW_T), 0, s, hw, map, keys, dst);
-    return view_launched("view_scalar kernels");
+    return launched("view_scalar kernels");
 }
 
 int surfel_view_gradient(int H, int W, const float* planes, float scale, float bias, uint8_t* dst, void* scratch, int64_t scratch_bytes,
@@ -187,7 +182,7 @@ int surfel_view_gradient(int H, int W, const float* planes, float scale, float b
     hipLaunchKernelGGL(view_reset_kernel, dim3(1), dim3(64), 0, s, keys);
     hipLaunchKernelGGL(view_gradient_kernel, dim3((W + VW_TW - 1) / VW_TW, (H + VW_TH - 1) / VW_TH), dim3(VW_T), 0, s, H, W, planes, scale, bias, m, keys);
     hipLaunchKernelGGL(view_colour_kernel, dim3(view_blocks(hw)), dim3(VW_T), 0, s, hw, m, keys, dst);
-    return view_launched("view_gradient kernels");
+    return launched("view_gradient kernels");
 }
 
 }  // extern "C"

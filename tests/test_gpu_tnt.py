@@ -65,6 +65,18 @@ def test_crop_matches_the_oracle_exactly():
 
 
 # ------------------------------------------------------------------------------------------------ 2: voxel down-sampling
+def _lattice_cloud():
+    """399 points in the 300 cells (x, y, z), x, y < 10, z < 2, and (x, y + 2048, 0) at voxel 1 (a third of the cells holds two points;
+    the first point is the minimum corner, so the origin is 0)."""
+    rng = np.random.default_rng(22)
+    g = np.stack(np.meshgrid(np.arange(10), np.arange(10), np.arange(2), indexing="ij"), -1).reshape(-1, 3)
+    cells = np.concatenate([g, g[g[:, 2] == 0] + [0, 2048, 0]])
+    cells = np.concatenate([cells, cells[::3][1:]])
+    pts = cells + rng.uniform(0.5, 0.95, size=cells.shape)
+    pts[0] = 0.5
+    return np.concatenate([pts[:1], pts[1:][rng.permutation(len(pts) - 1)]]).astype(np.float32)
+
+
 def _voxel_cases():
     rng = np.random.default_rng(21)
     yield "random, negative coordinates", rng.uniform(-3, 2, size=(20000, 3)).astype(np.float32), 0.1
@@ -74,6 +86,9 @@ def _voxel_cases():
     # two clusters 1500 apart along every axis at voxel 2^-10: 1.5 M cells per axis, a key far beyond 32 bits
     far = np.concatenate([rng.uniform(0, 0.5, size=(3000, 3)), rng.uniform(0, 0.5, size=(3000, 3)) + 1500.0]).astype(np.float32)
     yield "two clusters, 63-bit keys", far[rng.permutation(len(far))], 2.0 ** -10
+    # cells (x, y, z), (x, y, z + 1) and (x, y + 2048, z) share the key's low word (x and the low 11 bits of y) and differ in every part
+    # of its high word: the second sort pass alone orders them, and it has to keep the first pass's order inside a cell
+    yield "lattice, equal low words", _lattice_cloud(), 1.0
     yield "one point", np.array([[1.5, -2.0, 3.0]], np.float32), 0.25
     yield "empty", np.zeros((0, 3), np.float32), 0.25
     yield "100 000 points in one cell", (rng.uniform(0, 1, size=(100000, 3)) * 0.01 + [5.0, 6.0, -7.0]).astype(np.float32), 1.0
@@ -98,6 +113,8 @@ def test_voxel_down_sample_matches_the_oracle():
             assert all(key[i] < key[i + 1] for i in range(len(key) - 1))
             if "63-bit" in name:
                 assert max(key) >= 1 << 32 and wcells.max() > 1 << 20
+            if "low words" in name:
+                assert len(want) == 300 and len({int(k) & 0xFFFFFFFF for k in key}) == 100 and wcells[:, 1].max() >= 2048 and wcounts.max() == 2
             if "one cell" in name:
                 assert len(want) == 1 and wcounts[0] == 100000
             if "faces" in name:

@@ -274,3 +274,13 @@ def test_mesh_kernels_no_scratch():
     assert len(names) >= 15, names
     for k in names:
         assert int(ks[k][1].get("private_segment_fixed_size", 0)) == 0, k
+
+
+def test_scan_kernels_no_scratch():
+    sys.path.insert(0, os.path.join(REPO, "scripts"))
+    import isa_count
+    ks = isa_count.kernels(isa_count.assemble("device_scan.hip"))
+    for want in ("scan_sums_kernel", "scan_top_kernel", "scan_apply_kernel"):
+        names = [k for k in ks if want in k]
+        assert len(names) == 1, (want, list(ks))
+        assert ks[names[0]][1]["private_segment_fixed_size"] == 0, want
