@@ -158,7 +158,9 @@ __global__ void __launch_bounds__(KNN_BLOCK) knn_search_kernel(int P, int nboxes
             }
         }
     }
-    if (valid) out[idx_sorted[i]] = (b0 + b1 + b2) / 3.0f;
+    // fewer than three neighbours (P <= 3): a seed is left in b2 and the mean is +inf.  The fp32 sum alone says so only while two seeds
+    // are left (FLT_MAX + FLT_MAX overflows); with one, (b0 + b1) + FLT_MAX rounds back to FLT_MAX and would give a finite FLT_MAX / 3.
+    if (valid) out[idx_sorted[i]] = b2 == FLT_MAX ? INFINITY : (b0 + b1 + b2) / 3.0f;
 }
 
 struct KnnScratch {

@@ -471,6 +471,7 @@ int surfel_set_option(const char* name, int value) {
     if (name && std::strcmp(name, "tile_depth_sort") == 0) { g_opt_tile_sort = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
     if (name && std::strcmp(name, "large_sort") == 0) { set_large_sort_impl(value); return 0; }
     if (name && std::strcmp(name, "fwd_pipe") == 0) { set_fwd_pipe(value); return 0; }
+    if (name && std::strcmp(name, "preprocess_dma") == 0) { set_preprocess_dma(value); return 0; }
     if (name && std::strcmp(name, "bwd_variant") == 0) { g_opt_bwd_variant = value < 0 ? 0 : (value > 3 ? 3 : value); return 0; }
     if (name && std::strcmp(name, "tile_stream") == 0) { g_opt_stream = value != 0; return 0; }
     if (name && std::strcmp(name, "capacity_binning") == 0) { g_opt_capacity = value != 0; return 0; }

@@ -71,6 +71,7 @@ struct PreprocessBwdArgs {
 };
 
 void launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t s);
+void set_preprocess_dma(int v);       // SH block by LDS-DMA (preprocess_fwd_kernel<true>): 0 never, 1 (default) frames of >= 2^19 surfels, 2 always (tests, measurement)
 void launch_emit_instances(int P, float* rec, const uint32_t* rects, const uint32_t* order, uint32_t id_mask, const uint32_t* offsets_sorted, uint32_t* keys,
                            uint32_t* vals, int gx, uint32_t* zero_ptr, uint32_t zero_words, hipStream_t s);
 void launch_tile_ranges(int64_t R, const uint32_t* keys, uint2* ranges, hipStream_t s);

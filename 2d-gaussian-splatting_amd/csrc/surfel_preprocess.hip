@@ -1018,9 +1018,11 @@ __global__ void __launch_bounds__(256, PRE_BWD_MINWG) preprocess_bwd_kernel(Prep
 }
 
 // ------------------------------------------------------------------------------- launchers
+static int g_preprocess_dma = 1;      // surfel_set_option("preprocess_dma", .): 0 never, 1 by size (default: P >= 2^19), 2 always
+void set_preprocess_dma(int v) { g_preprocess_dma = v < 0 ? 0 : (v > 2 ? 2 : v); }      // 2: tests and measurement only (48 KB of LDS cost small frames 1 us)
 void launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t s) {
     if (a.P <= 0) return;
-    if (a.P >= (1 << 19)) hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3((a.P + 255) / 256), dim3(256), 0, s, a);
+    if (g_preprocess_dma == 2 || (g_preprocess_dma == 1 && a.P >= (1 << 19))) hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3((a.P + 255) / 256), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3((a.P + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_emit_instances(int P, float* rec, const uint32_t* rects, const uint32_t* order, uint32_t id_mask, const uint32_t* offsets_sorted, uint32_t* keys,

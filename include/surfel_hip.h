@@ -87,7 +87,7 @@ int surfel_rasterize_backward(
 int surfel_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present, void* stream);
 /* Replaces `simple_knn._C.distCUDA2` (/root/reference/scene/gaussian_model.py:20,134): mean squared distance to the 3 nearest neighbours. */
 int surfel_knn_dist2(surfel_alloc_fn scratch_alloc, void* scratch_user, int P, const float* points, float* mean_dist2, void* stream);
-/* Process-wide defaults of the eight switches below; returns 0, or SURFEL_E_INVALID for an unknown name.  None changes a result bit except
+/* Process-wide defaults of the nine switches below; returns 0, or SURFEL_E_INVALID for an unknown name.  None changes a result bit except
  * where stated; each default is the measured best; the other settings serve the identity tests and A / B runs.
  *   "cull"             1   exact footprint culling (tile emission and per-sub-tile masks restricted to the alpha >= 1/255 footprint); 0: every pair of the reference's tile rectangles
  *   "tile_depth_sort"  1   binning path: 2 surfel-order emission + per-tile depth sort in LDS, 0 depth-presorted emission, 1 by the previous frame's instances per tile
@@ -95,6 +95,7 @@ int surfel_knn_dist2(surfel_alloc_fn scratch_alloc, void* scratch_user, int P, c
  *   "large_sort"       2   sorts of > 2^20 items: 0 own three-launch passes, 1 rocprim::radix_sort_pairs, 2 rocPRIM above 2^25 items
  *   "tile_order"       0   which tile a blend workgroup takes: 1 XCD-contiguous runs, 2 longest lists first over the XCDs, 0 decided per frame on the device
  *   "fwd_pipe"         1   blend forward with LDS-DMA double-buffered staging (0: the batch-synchronous kernel, same bits)
+ *   "preprocess_dma"   1   preprocess reads a wave's SH block by LDS-DMA (same bits): 0 never, 1 frames of >= 2^19 surfels, 2 always (tests and measurement)
  *   "tile_stream"      1   blend_fwd leaves the walked records + footprint bits in list order (84 B x binning capacity, frames <= 2^24 instances) for blend_bwd's staging
  *   "bwd_variant"      2   blend-backward walk: 0 per-row, 1 per-quad (bit-identical to 0), 3 scan (deterministic; agrees to fp32 summation noise), 2 = 0 or 3 by a rule on the frame alone
  */

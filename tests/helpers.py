@@ -102,3 +102,41 @@ def cosine(x, ref):
     x = np.asarray(x, np.float64).ravel(); ref = np.asarray(ref, np.float64).ravel()
     d = np.linalg.norm(x) * np.linalg.norm(ref)
     return float(x @ ref / d) if d > 0 else 1.0
+
+
+# The small-scene checks against the fp64 oracle (tests/test_gpu_parity.py states the tolerances; determinacy.py holds the constants).
+def check_binning(run, R, radii):
+    """Small scenes: radii exact.  The device emits a (tile, surfel) instance only where the surfel's alpha >= 1/255 bbox reaches the
+    tile, so its instance count is a subset of the reference rect count the oracle reports.  (Config sizes: determinacy.judge_radii.)"""
+    got = run.radii.cpu().numpy()
+    assert np.array_equal(got, radii) and run.R <= R, (int((got != radii).sum()), run.R, R)
+
+
+def check_images(run, col, oth, st):
+    import determinacy as D
+    c = run.color.cpu().numpy(); o = run.others.cpu().numpy()
+    assert np.isfinite(c).all() and np.isfinite(o).all()
+    assert frac_close(c, col, D.IMG_ATOL, D.IMG_RTOL) >= D.PASS_FRAC, "color"
+    for ch, nm in [(0, "depth-sum"), (1, "alpha"), (2, "nx"), (3, "ny"), (4, "nz"), (6, "distortion")]:
+        f = frac_close(o[ch], oth[ch], D.IMG_ATOL, D.IMG_RTOL)
+        assert f >= D.PASS_FRAC, "%s: only %.5f of pixels within tolerance" % (nm, f)
+    assert frac_close(o[5], oth[5], 1e-4, 1e-4) >= D.PASS_FRAC, "median depth"
+
+
+def check_grads(g, og, has_sr=True):
+    import determinacy as D
+    pairs = [("means3D", og.dL_dmeans3D), ("opacity", og.dL_dopacity), ("sh", og.dL_dsh), ("means2D", og.dL_dmean2D)]
+    if has_sr:
+        pairs += [("scales", og.dL_dscales), ("rots", og.dL_drots)]
+    for k, ref in pairs:
+        x = g[k].reshape(ref.shape)
+        assert np.isfinite(x).all(), k
+        scale = np.abs(ref).mean() + 1e-30
+        f = frac_close(x, ref, 1e-4 * scale + 1e-12, D.G_RTOL)
+        cs = cosine(x, ref)
+        # a (pixel, surfel) pair sitting exactly on the 1/255 or 1e-4 threshold may be decided differently in fp32;
+        # that moves ONE surfel's gradient, so small scenes get an absolute allowance of 3 surfels
+        bad = np.abs(x.astype(np.float64) - ref) > (1e-4 * scale + 1e-12 + D.G_RTOL * np.abs(ref))
+        bad_surfels = int(bad.reshape(bad.shape[0], -1).any(1).sum())
+        assert f >= D.PASS_FRAC or bad_surfels <= 3, "%s: only %.5f of elements within tolerance, %d surfels (cos %.7f)" % (k, f, bad_surfels, cs)
+        assert cs >= D.COS_MIN, "%s: cosine %.7f" % (k, cs)

@@ -19,6 +19,7 @@ import pytest
 
 import determinacy as D
 from helpers import HipRun, cosine, frac_close, oracle_forward, scene_args
+from helpers import check_binning as _check_binning, check_grads as _check_grads, check_images as _check_images
 
 pytestmark = pytest.mark.gpu
 
@@ -38,41 +39,6 @@ def _scene(name_or_dims, seed=0, **kw):
         P, W, H = name_or_dims
         sc = synthetic.make_scene(P, W, H, seed=seed, **kw)
     return sc
-
-
-def _check_binning(run, R, radii):
-    """Small scenes: radii exact.  The device emits a (tile, surfel) instance only where the surfel's alpha >= 1/255 bbox reaches the
-    tile, so its instance count is a subset of the reference rect count the oracle reports.  (Config sizes: determinacy.judge_radii.)"""
-    got = run.radii.cpu().numpy()
-    assert np.array_equal(got, radii) and run.R <= R, (int((got != radii).sum()), run.R, R)
-
-
-def _check_images(run, col, oth, st):
-    c = run.color.cpu().numpy(); o = run.others.cpu().numpy()
-    assert np.isfinite(c).all() and np.isfinite(o).all()
-    assert frac_close(c, col, IMG_ATOL, IMG_RTOL) >= IMG_FRAC, "color"
-    for ch, nm in [(0, "depth-sum"), (1, "alpha"), (2, "nx"), (3, "ny"), (4, "nz"), (6, "distortion")]:
-        f = frac_close(o[ch], oth[ch], IMG_ATOL, IMG_RTOL)
-        assert f >= IMG_FRAC, "%s: only %.5f of pixels within tolerance" % (nm, f)
-    assert frac_close(o[5], oth[5], 1e-4, 1e-4) >= IMG_FRAC, "median depth"
-
-
-def _check_grads(g, og, has_sr=True):
-    pairs = [("means3D", og.dL_dmeans3D), ("opacity", og.dL_dopacity), ("sh", og.dL_dsh), ("means2D", og.dL_dmean2D)]
-    if has_sr:
-        pairs += [("scales", og.dL_dscales), ("rots", og.dL_drots)]
-    for k, ref in pairs:
-        x = g[k].reshape(ref.shape)
-        assert np.isfinite(x).all(), k
-        scale = np.abs(ref).mean() + 1e-30
-        f = frac_close(x, ref, 1e-4 * scale + 1e-12, G_RTOL)
-        cs = cosine(x, ref)
-        # a (pixel, surfel) pair sitting exactly on the 1/255 or 1e-4 threshold may be decided differently in fp32;
-        # that moves ONE surfel's gradient, so small scenes get an absolute allowance of 3 surfels
-        bad = np.abs(x.astype(np.float64) - ref) > (1e-4 * scale + 1e-12 + G_RTOL * np.abs(ref))
-        bad_surfels = int(bad.reshape(bad.shape[0], -1).any(1).sum())
-        assert f >= G_FRAC or bad_surfels <= 3, "%s: only %.5f of elements within tolerance, %d surfels (cos %.7f)" % (k, f, bad_surfels, cs)
-        assert cs >= G_COS, "%s: cosine %.7f" % (k, cs)
 
 
 @pytest.mark.parametrize("dims,kw", [((512, 72, 56), dict(seed=7, px_radius=4.0, z_near=1.0, z_far=6.0)),

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPTIONS = {"cull": 1, "tile_depth_sort": 1, "capacity_binning": 1, "large_sort": 2, "tile_order": 0, "fwd_pipe": 1, "tile_stream": 1, "bwd_variant": 2}
+OPTIONS = {"cull": 1, "tile_depth_sort": 1, "capacity_binning": 1, "large_sort": 2, "tile_order": 0, "fwd_pipe": 1, "preprocess_dma": 1, "tile_stream": 1, "bwd_variant": 2}
 REMOVED = ["bwd_split", "bwd_tune", "scan_large", "host_total", "fat_sort", "pbwd_coop"]
 
 
@@ -28,13 +28,13 @@ def test_documented_option_is_accepted_with_its_default(name):
 
 
 def test_the_header_documents_exactly_the_accepted_options():
-    """<= 8 documented options (VERDICT r4 #6), none undocumented: the names in the header's option table are the library's"""
+    """<= 9 documented options (VERDICT r4 #6 set 8; "preprocess_dma" is the ninth), none undocumented: the names in the header's option table are the library's"""
     import surfel_native
     lib = surfel_native.load()
     hdr = _header()
-    blk = hdr[hdr.index("Process-wide defaults of the eight switches"):hdr.index("int surfel_set_option")]
+    blk = hdr[hdr.index("Process-wide defaults of the nine switches"):hdr.index("int surfel_set_option")]
     names = re.findall(r'^ \*   "([a-z_]+)"', blk, flags=re.M)
-    assert sorted(names) == sorted(OPTIONS) and len(names) <= 8
+    assert sorted(names) == sorted(OPTIONS) and len(names) <= 9
     src = open(os.path.join(REPO, "2d-gaussian-splatting_amd", "csrc", "surfel_api.hip")).read()
     accepted = re.findall(r'std::strcmp\(name, "([a-z_]+)"\) == 0', src)
     assert sorted(accepted) == sorted(OPTIONS)
