@@ -434,7 +434,7 @@ def _scene_cameras(args, gaussians, it):
     args.white_background = args.white_background or getattr(cfg, "white_background", False)      # renders over what the images were composited on
     scene = Scene(args.source_path, args.model_path, images=getattr(cfg, "images", "images"), resolution=getattr(cfg, "resolution", -1),
                   white_background=args.white_background, eval=getattr(cfg, "eval", False),
-                  data_device=str(gaussians.device), load_iteration=it, shuffle=False, gaussians=gaussians)
+                  data_device=str(gaussians.device), load_iteration=it, shuffle=False, gaussians=gaussians, decode=getattr(args, "decode", "host"))
     return scene.getTrainCameras(), scene.getTestCameras()
 
 
@@ -469,6 +469,8 @@ def build_parser():
     ap.add_argument("--fps", default=60, type=int, help="Path: frame rate of the videos")
     ap.add_argument("--png", default="pillow", choices=["pillow", "device"], help="who encodes the PNG files of --render_path and of the renders / gt "
                     "export: Pillow on host threads (the default) or the encoder on the device (PNG.md); the same names and pixels")
+    ap.add_argument("--decode", default="host", choices=["host", "device"], help="with -s: who decodes the capture's JPEG files: Pillow on the host "
+                    "(the default) or the decoder on the device (JPEGDEC.md); the same cameras")
     return ap
 
 

@@ -64,11 +64,19 @@ class EvalGrid(C.Structure):
                 ("sorted", C.c_void_p), ("order", C.c_void_p), ("ranges", C.c_void_p)]
 
 
+class JpegDecDesc(C.Structure):
+    """surfel_jpegdec_desc of include/surfel_jpegdec.h (a host structure: what surfel_jpegdec.parse found in the file's segments)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("restart_interval", C.c_int32), ("ecs_offset", C.c_int64), ("ecs_bytes", C.c_int64),
+                ("tq", C.c_uint8 * 4), ("td", C.c_uint8 * 4), ("ta", C.c_uint8 * 4), ("qt", (C.c_uint16 * 64) * 4),
+                ("bits", (C.c_uint8 * 16) * 4), ("huffval", (C.c_uint8 * 256) * 4)]
+
+
 # ---- every exported function: name -> (restype, parameter types ...), grouped by the header that declares it.  d = device pointer,
 # s = the stream, u = any other void*, a = allocator callback; host pointers keep their POINTER(...) type.
 _i, _i64, _f, _f64, _d, _s, _u, _a = C.c_int, C.c_int64, C.c_float, C.c_double, DevPtr, Stream, C.c_void_p, ALLOC_FN
 _fp, _ip, _i64p, _f64p = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
-_vol, _uvol, _grid = C.POINTER(TsdfVolume), C.POINTER(UnboundedVolume), C.POINTER(EvalGrid)
+_vol, _uvol, _grid, _jdesc = C.POINTER(TsdfVolume), C.POINTER(UnboundedVolume), C.POINTER(EvalGrid), C.POINTER(JpegDecDesc)
 _adam = (_i, _d, _d, _d, _d, _d, _fp, _f, _f, _f, _i, _f, _i, _i, _d, _d)      # surfel_adam_step up to gcol_all
 SIGNATURES = {
     "surfel_hip.h": {
@@ -193,6 +201,10 @@ SIGNATURES = {
         "surfel_png_scratch_bytes": (_i64, _i, _i, _i),
         "surfel_png_encode": (_i, _i, _i, _i, _d, _d, _i64, _d, _d, _i64, _s),
     },
+    "surfel_jpegdec.h": {
+        "surfel_jpegdec_scratch_bytes": (_i64, _jdesc, _i),
+        "surfel_jpegdec_decode": (_i, _jdesc, _d, _i64, _d, _d, _i64, _i, _i, _i, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -206,6 +218,7 @@ VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
+JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

@@ -5,7 +5,8 @@ model-folder layout (`input.ply`, `cameras.json`, `point_cloud/iteration_N`) tha
 The host decodes (PIL) and parses; everything after the decode is HIP (include/surfel_scene.h): the decoded u8 HWC image is uploaded once,
 resampled with Pillow's 8-bit BICUBIC arithmetic (bit for bit what `pil_image.resize(resolution)` returns), composited over the
 background (Blender), and converted to planar fp32 with the alpha channel split off as the mask.  There is no host fallback: a CPU
-tensor or device is refused by the library's boundary.
+tensor or device is refused by the library's boundary.  With decode="device" the JPEG files are decoded in HIP too (JPEGDEC.md): the
+threads read and parse them, the file's bytes are what is uploaded, and a file the decoder does not take goes to PIL as before.
 """
 import collections
 import ctypes as C
@@ -415,43 +416,83 @@ def _decode_file(info):
         return decode(im.convert("RGBA") if info.composite else im)
 
 
-def _decoded(infos, workers):
+def _pillow_bytes(data):
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return decode(im)
+
+
+def _read_file(info):
+    """decode="device": ("device", file bytes, descriptor) for a JPEG file the device decoder takes (surfel_jpegdec.parse: no entropy
+    decoding here), ("fallback", pixels) for a JPEG file it does not take, ("host", pixels) for everything else."""
+    import surfel_jpegdec
+    if info.composite or os.path.splitext(info.image_path)[1].lower() not in (".jpg", ".jpeg"):
+        return ("host", _decode_file(info))
+    with open(info.image_path, "rb") as f:
+        data = f.read()
+    desc = surfel_jpegdec.parse(data)
+    if desc is None:
+        return ("fallback", _pillow_bytes(data))
+    return ("device", data, desc)
+
+
+def _decoded(infos, workers, decode_file=_decode_file):
     """decoded images in camera order; at most 2 x workers of them are in flight"""
     workers = max(1, min(int(workers), MAX_WORKERS))
     with ThreadPoolExecutor(workers) as pool:
         pending = collections.deque()
         it = iter(infos)
         for info in it:
-            pending.append(pool.submit(_decode_file, info))
+            pending.append(pool.submit(decode_file, info))
             if len(pending) >= 2 * workers:
                 break
         while pending:
             yield pending.popleft().result()
             for info in it:
-                pending.append(pool.submit(_decode_file, info))
+                pending.append(pool.submit(decode_file, info))
                 break
 
 
 _warned_large = False
 
 
-def load_cameras(infos, resolution=-1, white_background=False, data_device="cuda", workers=4):
+def load_cameras(infos, resolution=-1, white_background=False, data_device="cuda", workers=4, decode="host", *, decode_options=None):
     """surfel_render.Camera list of utils/camera_utils.py:41-62 (cameraList_from_camInfos): the decode runs on `workers` threads, the
-    device work on the calling thread in camera order."""
+    device work on the calling thread in camera order.  decode="device" (JPEGDEC.md): the threads only read and parse .jpg / .jpeg
+    files, and the calling thread uploads each file and decodes it on the device (surfel_jpegdec.decode_jpeg); a file the decoder does not take, or reports as not converged or damaged, is decoded by Pillow as with
+    decode="host".  The cameras do not depend on `decode` or `workers`.  decode_options (keyword only, for the tests: Scene and the
+    CLIs do not pass it): decode_jpeg's subseq_bits / max_rounds, to make the subsequences short or the rounds run out."""
     global _warned_large
+    if decode not in ("host", "device"):
+        raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
     cams = []
-    for id, (info, u8) in enumerate(zip(infos, _decoded(infos, workers))):
+    fallbacks = 0
+    for id, (info, item) in enumerate(zip(infos, _decoded(infos, workers, _read_file if decode == "device" else _decode_file))):
+        u8 = item
+        if decode == "device":
+            u8 = item[1]
+            fallbacks += item[0] == "fallback"
+            if item[0] == "device":
+                import surfel_jpegdec
+                try:
+                    u8 = surfel_jpegdec.decode_jpeg(item[1], data_device, desc=item[2], **(decode_options or {}))
+                except surfel_jpegdec.JpegNotDecoded:
+                    u8, fallbacks = _pillow_bytes(item[1]), fallbacks + 1
         h, w = u8.shape[:2]
         if resolution == -1 and w > 1600 and not _warned_large:
             print("[ INFO ] Encountered quite large input images (>1.6K pixels width), rescaling to 1.6K.\n "
                   "If this is not desired, please explicitly specify '--resolution/-r' as 1")
             _warned_large = True
-        src = torch.from_numpy(u8).to(data_device)
+        src = u8 if torch.is_tensor(u8) else torch.from_numpy(u8).to(data_device)
         if info.composite:
             src = composite(src, white_background)
         image, mask = load_image(src, target_resolution(w, h, resolution), data_device)
         cams.append(Camera(colmap_id=info.uid, R=info.R, T=info.T, FoVx=info.FovX, FoVy=info.FovY, image=image, gt_alpha_mask=mask,
                            image_name=info.image_name, uid=id, data_device=data_device))
+    if fallbacks:
+        print("[ INFO ] %d of %d images: JPEG files outside the device decoder's scope (or reported not converged / damaged), decoded by Pillow"
+              % (fallbacks, len(cams)))
     return cams
 
 
@@ -461,7 +502,7 @@ class Scene:
     capture's points.  Results do not depend on `workers`."""
 
     def __init__(self, source_path, model_path, images="images", resolution=-1, white_background=False, eval=False, data_device="cuda",
-                 load_iteration=None, shuffle=True, seed=0, workers=4, gaussians=None, sh_degree=3):
+                 load_iteration=None, shuffle=True, seed=0, workers=4, gaussians=None, sh_degree=3, decode="host"):
         from surfel_model import GaussianModel
         self.model_path = model_path
         self.loaded_iter = None
@@ -480,8 +521,8 @@ class Scene:
             rng.shuffle(train)
             rng.shuffle(test)
         self.cameras_extent = float(info.nerf_normalization["radius"])
-        self.train_cameras = load_cameras(train, resolution, white_background, data_device, workers)
-        self.test_cameras = load_cameras(test, resolution, white_background, data_device, workers)
+        self.train_cameras = load_cameras(train, resolution, white_background, data_device, workers, decode)
+        self.test_cameras = load_cameras(test, resolution, white_background, data_device, workers, decode)
         self.gaussians = gaussians if gaussians is not None else GaussianModel(sh_degree, device=torch.device(data_device))
         if self.loaded_iter:
             self.gaussians.load_ply(os.path.join(model_path, "point_cloud", "iteration_%d" % self.loaded_iter, "point_cloud.ply"))

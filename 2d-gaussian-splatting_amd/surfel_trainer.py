@@ -638,6 +638,8 @@ def parse_args(argv=None):
     ap.add_argument("--start_checkpoint", type=str, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--workers", type=int, default=4, help="image decoding threads (at most 8)")
+    ap.add_argument("--decode", default="host", choices=["host", "device"], help="who decodes the capture's JPEG files: Pillow on the host threads "
+                    "(the default) or the decoder on the device (JPEGDEC.md); the same cameras")
     args = ap.parse_args(argv)
     args.save_iterations = list(args.save_iterations) + [args.iterations]
     args.source_path = os.path.abspath(args.source_path)
@@ -696,7 +698,7 @@ def main(argv=None):
     write_cfg_args(args)
     opt, pipe = optimization_from_args(args), pipeline_params(depth_ratio=args.depth_ratio)
     scene = Scene(args.source_path, args.model_path, images=args.images, resolution=args.resolution, white_background=args.white_background,
-                  eval=args.eval, data_device=args.data_device, seed=args.seed, workers=args.workers, sh_degree=args.sh_degree)
+                  eval=args.eval, data_device=args.data_device, seed=args.seed, workers=args.workers, sh_degree=args.sh_degree, decode=args.decode)
     model, first_iter = scene.gaussians, 0
     model.training_setup(opt)
     if args.start_checkpoint:
