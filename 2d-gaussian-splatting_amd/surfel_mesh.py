@@ -425,7 +425,7 @@ def _latest_iteration(model_dir):
 
 def _scene_cameras(args, gaussians, it):
     """(train, test) cameras of the capture at args.source_path, loaded the way the training run loaded them: images folder, resolution,
-    split and background from model_path/cfg_args (surfel_trainer.write_cfg_args) where it exists."""
+    split, background and undistortion from model_path/cfg_args (surfel_trainer.write_cfg_args) where it exists."""
     from surfel_scene import Scene
     cfg = argparse.Namespace(images="images", resolution=-1, eval=False, white_background=False)
     path = os.path.join(args.model_path, "cfg_args")
@@ -434,7 +434,8 @@ def _scene_cameras(args, gaussians, it):
     args.white_background = args.white_background or getattr(cfg, "white_background", False)      # renders over what the images were composited on
     scene = Scene(args.source_path, args.model_path, images=getattr(cfg, "images", "images"), resolution=getattr(cfg, "resolution", -1),
                   white_background=args.white_background, eval=getattr(cfg, "eval", False),
-                  data_device=str(gaussians.device), load_iteration=it, shuffle=False, gaussians=gaussians, decode=getattr(args, "decode", "host"))
+                  data_device=str(gaussians.device), load_iteration=it, shuffle=False, gaussians=gaussians, decode=getattr(args, "decode", "host"),
+                  undistort=bool(getattr(args, "undistort", False) or getattr(cfg, "undistort", False)))
     return scene.getTrainCameras(), scene.getTestCameras()
 
 
@@ -455,6 +456,8 @@ def build_parser():
     ap.add_argument("--budget_gb", default=DEFAULT_BUDGET / 2 ** 30, type=float, help="byte budget of the TSDF volume (GiB)")
     ap.add_argument("-s", "--source_path", default=None, help="the capture the model was trained on: cameras and ground-truth images come from it "
                     "(surfel_scene.Scene, with the model's cfg_args), only the training split is fused, and renders / gt of both splits are exported")
+    ap.add_argument("--undistort", action="store_true", help="with -s: undistort the capture while it is loaded (UNDISTORT.md); implied by a model "
+                    "folder that was trained with --undistort")
     ap.add_argument("--skip_train", action="store_true", help="with -s: do not export the training split's renders / gt")
     ap.add_argument("--skip_test", action="store_true", help="with -s: do not export the test split's renders / gt")
     ap.add_argument("--skip_mesh", action="store_true", help="do not extract a mesh")

@@ -205,6 +205,9 @@ SIGNATURES = {
         "surfel_jpegdec_scratch_bytes": (_i64, _jdesc, _i),
         "surfel_jpegdec_decode": (_i, _jdesc, _d, _i64, _d, _d, _i64, _i, _i, _i, _d, _s),
     },
+    "surfel_undistort.h": {
+        "surfel_scene_undistort": (_i, _i, _i, _i, _i, _i, _f64p, _f64p, _d, _d, _s),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -219,6 +222,7 @@ CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])
+UNDISTORT_EXPORTS = list(SIGNATURES["surfel_undistort.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

@@ -7,6 +7,9 @@ resampled with Pillow's 8-bit BICUBIC arithmetic (bit for bit what `pil_image.re
 background (Blender), and converted to planar fp32 with the alpha channel split off as the mask.  There is no host fallback: a CPU
 tensor or device is refused by the library's boundary.  With decode="device" the JPEG files are decoded in HIP too (JPEGDEC.md): the
 threads read and parse them, the file's bytes are what is uploaded, and a file the decoder does not take goes to PIL as before.
+With undistort=True a COLMAP capture whose cameras are SIMPLE_RADIAL, RADIAL, OPENCV or FULL_OPENCV is undistorted on the way in
+(UNDISTORT.md, surfel_undistort.py): the reader hands out the undistorted pinhole cameras, and every decoded image passes through the
+undistortion kernel before anything else is done to it.
 """
 import collections
 import ctypes as C
@@ -23,6 +26,7 @@ import torch
 
 import surfel_io
 import surfel_native as _n
+import surfel_undistort
 from surfel_render import Camera, world2view
 
 MAX_WORKERS = 8
@@ -155,6 +159,9 @@ class CameraInfo(NamedTuple):
     width: int
     height: int
     composite: bool = False  # Blender: RGBA over the background before anything else
+    distortion: np.ndarray = None   # undistort=True on a distorted COLMAP camera: q[12] of UNDISTORT.md; width, height and FoV above are the undistorted ones
+    pinhole: tuple = None           # ... and the undistorted camera (fx, fy, cx2, cy2) the image is resampled into
+    source_size: tuple = None       # ... and the (width, height) the COLMAP camera, and so the file, must have
 
 
 class PointCloud(NamedTuple):
@@ -208,7 +215,8 @@ def camera_to_json(id, cam):
 
 
 # ------------------------------------------------------------------------------------------------ COLMAP models
-# model id -> (name, number of parameters); only the two undistorted pinhole models are accepted downstream
+# model id -> (name, number of parameters); downstream accepts the two undistorted pinhole models, and with undistort=True those of
+# surfel_undistort.MODELS
 COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8),
                  6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 
@@ -325,29 +333,51 @@ def _image_size(path):
         return im.size
 
 
-def read_colmap_scene(path, images="images", eval=False, llffhold=LLFFHOLD):
+def _has_model(sparse):
+    return any(os.path.exists(os.path.join(sparse, name)) for name in ("cameras.bin", "cameras.txt"))
+
+
+def read_colmap_scene(path, images="images", eval=False, llffhold=LLFFHOLD, undistort=False):
     """scene/dataset_readers.py:132-177: sparse/0/{cameras,images,points3D}.bin (else .txt), cameras sorted by image name, every
-    llffhold-th of them held out under eval, points3D converted to points3D.ply on first open."""
+    llffhold-th of them held out under eval, points3D converted to points3D.ply on first open.
+    undistort=True (UNDISTORT.md): a camera of a model in surfel_undistort.MODELS yields the undistorted pinhole camera's width, height
+    and FoV, with the distortion carried along for load_cameras; pinhole cameras are untouched.  The model is sparse/0, else
+    distorted/sparse/0, and the images are the `images` folder, else input/ (convert.py's layout before its undistortion step)."""
     sparse = os.path.join(path, "sparse/0")
+    if undistort and not _has_model(sparse) and _has_model(os.path.join(path, "distorted/sparse/0")):
+        sparse = os.path.join(path, "distorted/sparse/0")
     if os.path.exists(os.path.join(sparse, "images.bin")) and os.path.exists(os.path.join(sparse, "cameras.bin")):
         extr, intr = read_images_bin(os.path.join(sparse, "images.bin")), read_cameras_bin(os.path.join(sparse, "cameras.bin"))
     else:
         extr, intr = read_images_txt(os.path.join(sparse, "images.txt")), read_cameras_txt(os.path.join(sparse, "cameras.txt"))
     folder = os.path.join(path, "images" if images is None else images)
+    if undistort and not os.path.isdir(folder):
+        folder = os.path.join(path, "input")
     infos = []
+    undistorted = {}      # COLMAP camera id -> (q, (W2, H2, fx, fy, cx2, cy2)): the rule runs once per camera
     for im in extr.values():
         cam = intr[im.camera_id]
+        width, height, extra = cam.width, cam.height, {}
         if cam.model == "SIMPLE_PINHOLE":
             fx = fy = cam.params[0]
         elif cam.model == "PINHOLE":
             fx, fy = cam.params[0], cam.params[1]
-        else:
+        elif not undistort:
             raise ValueError("COLMAP camera model %s is not supported: only undistorted captures (PINHOLE or SIMPLE_PINHOLE) are; run "
-                             "COLMAP's image_undistorter first" % cam.model)
+                             "COLMAP's image_undistorter first, or pass undistort=True (--undistort, UNDISTORT.md)" % cam.model)
+        elif cam.model not in surfel_undistort.MODELS:
+            raise ValueError("COLMAP camera model %s is not supported, with or without undistort: only %s can be undistorted here (the "
+                             "fisheye, FOV and thin-prism models need atan)" % (cam.model, ", ".join(surfel_undistort.MODELS)))
+        else:
+            if cam.id not in undistorted:
+                q = surfel_undistort.distortion_params(cam.model, cam.params)
+                undistorted[cam.id] = (q, surfel_undistort.undistorted_camera(q, cam.width, cam.height))
+            q, (width, height, fx, fy, cx2, cy2) = undistorted[cam.id]
+            extra = dict(distortion=q, pinhole=(fx, fy, cx2, cy2), source_size=(cam.width, cam.height))
         image_path = os.path.join(folder, os.path.basename(im.name))
-        infos.append(CameraInfo(uid=cam.id, R=np.transpose(qvec2rotmat(im.qvec)), T=np.array(im.tvec), FovY=focal2fov(fy, cam.height),
-                                FovX=focal2fov(fx, cam.width), image_path=image_path, image_name=os.path.basename(image_path).split(".")[0],
-                                width=cam.width, height=cam.height))
+        infos.append(CameraInfo(uid=cam.id, R=np.transpose(qvec2rotmat(im.qvec)), T=np.array(im.tvec), FovY=focal2fov(fy, height),
+                                FovX=focal2fov(fx, width), image_path=image_path, image_name=os.path.basename(image_path).split(".")[0],
+                                width=width, height=height, **extra))
     infos = sorted(infos, key=lambda c: c.image_name)
     train = [c for i, c in enumerate(infos) if not eval or i % llffhold != 0]
     test = [c for i, c in enumerate(infos) if eval and i % llffhold == 0]
@@ -396,10 +426,10 @@ def read_blender_scene(path, white_background=False, eval=False, seed=0, num_pts
     return SceneInfo(fetch_points_ply(ply_path), train, test, nerfpp_norm(train), ply_path)
 
 
-def read_scene_info(source_path, images="images", white_background=False, eval=False, seed=0):
-    """Scene-type detection of scene/__init__.py:43-49."""
-    if os.path.exists(os.path.join(source_path, "sparse")):
-        return read_colmap_scene(source_path, images, eval)
+def read_scene_info(source_path, images="images", white_background=False, eval=False, seed=0, undistort=False):
+    """Scene-type detection of scene/__init__.py:43-49; with undistort=True distorted/sparse alone also makes a COLMAP capture."""
+    if os.path.exists(os.path.join(source_path, "sparse")) or (undistort and os.path.exists(os.path.join(source_path, "distorted", "sparse"))):
+        return read_colmap_scene(source_path, images, eval, undistort=undistort)
     if os.path.exists(os.path.join(source_path, "transforms_train.json")):
         return read_blender_scene(source_path, white_background, eval, seed=seed)
     raise ValueError("could not recognize the scene type of %s: neither sparse/ (COLMAP) nor transforms_train.json (Blender)" % source_path)
@@ -461,7 +491,9 @@ def load_cameras(infos, resolution=-1, white_background=False, data_device="cuda
     """surfel_render.Camera list of utils/camera_utils.py:41-62 (cameraList_from_camInfos): the decode runs on `workers` threads, the
     device work on the calling thread in camera order.  decode="device" (JPEGDEC.md): the threads only read and parse .jpg / .jpeg
     files, and the calling thread uploads each file and decodes it on the device (surfel_jpegdec.decode_jpeg); a file the decoder does not take, or reports as not converged or damaged, is decoded by Pillow as with
-    decode="host".  The cameras do not depend on `decode` or `workers`.  decode_options (keyword only, for the tests: Scene and the
+    decode="host".  An info that carries a distortion (read_colmap_scene(undistort=True)) has its decoded image undistorted on the device
+    first (surfel_undistort.undistort); the -r rule and the size warning then see the undistorted size.  The cameras do not depend on
+    `decode` or `workers`.  decode_options (keyword only, for the tests: Scene and the
     CLIs do not pass it): decode_jpeg's subseq_bits / max_rounds, to make the subsequences short or the rounds run out."""
     global _warned_large
     if decode not in ("host", "device"):
@@ -479,6 +511,12 @@ def load_cameras(infos, resolution=-1, white_background=False, data_device="cuda
                     u8 = surfel_jpegdec.decode_jpeg(item[1], data_device, desc=item[2], **(decode_options or {}))
                 except surfel_jpegdec.JpegNotDecoded:
                     u8, fallbacks = _pillow_bytes(item[1]), fallbacks + 1
+        if info.distortion is not None:
+            if (int(u8.shape[1]), int(u8.shape[0])) != tuple(info.source_size):
+                raise ValueError("%s is %d x %d, but its COLMAP camera (%d) is %d x %d: the images are not the ones the model was built on"
+                                 % (info.image_path, u8.shape[1], u8.shape[0], info.uid, info.source_size[0], info.source_size[1]))
+            u8 = u8 if torch.is_tensor(u8) else torch.from_numpy(u8).to(data_device)
+            u8 = surfel_undistort.undistort(u8, info.distortion, info.pinhole, (info.width, info.height))
         h, w = u8.shape[:2]
         if resolution == -1 and w > 1600 and not _warned_large:
             print("[ INFO ] Encountered quite large input images (>1.6K pixels width), rescaling to 1.6K.\n "
@@ -499,16 +537,17 @@ def load_cameras(infos, resolution=-1, white_background=False, data_device="cuda
 class Scene:
     """scene/__init__.py:21-92 for one resolution scale.  On a fresh run writes input.ply and cameras.json (test cameras first, then train,
     ids by position) into model_path; load_iteration (-1: the latest) loads point_cloud/iteration_N instead of initialising from the
-    capture's points.  Results do not depend on `workers`."""
+    capture's points.  Results do not depend on `workers`.  undistort=True: a distorted COLMAP capture is undistorted while it is loaded
+    (UNDISTORT.md), and cameras.json carries the undistorted sizes and focal lengths."""
 
     def __init__(self, source_path, model_path, images="images", resolution=-1, white_background=False, eval=False, data_device="cuda",
-                 load_iteration=None, shuffle=True, seed=0, workers=4, gaussians=None, sh_degree=3, decode="host"):
+                 load_iteration=None, shuffle=True, seed=0, workers=4, gaussians=None, sh_degree=3, decode="host", undistort=False):
         from surfel_model import GaussianModel
         self.model_path = model_path
         self.loaded_iter = None
         if load_iteration:
             self.loaded_iter = search_max_iteration(os.path.join(model_path, "point_cloud")) if load_iteration == -1 else load_iteration
-        info = read_scene_info(source_path, images, white_background, eval, seed)
+        info = read_scene_info(source_path, images, white_background, eval, seed, undistort=undistort)
         train, test = list(info.train_cameras), list(info.test_cameras)
         if not self.loaded_iter:
             os.makedirs(model_path, exist_ok=True)

@@ -625,6 +625,8 @@ def parse_args(argv=None):
     g.add_argument("--sh_degree", default=3, type=int)
     g.add_argument("--data_device", default="cuda", type=str)
     g.add_argument("--eval", default=False, action="store_true")
+    g.add_argument("--undistort", default=False, action="store_true", help="undistort a COLMAP capture whose cameras are SIMPLE_RADIAL, RADIAL, OPENCV "
+                   "or FULL_OPENCV while it is loaded (UNDISTORT.md): sparse/0 else distorted/sparse/0, the -i folder else input/")
     g = ap.add_argument_group("Optimization Parameters")
     defaults = vars(optimization_params())
     for name in _OPTIMIZATION_ARGS:
@@ -652,13 +654,17 @@ def optimization_from_args(args):
 
 def write_cfg_args(args):
     """model_path/cfg_args = str(Namespace(...)) of the loading parameters (train.py:146-160), which the reference's render.py and
-    metrics.py evaluate back (arguments/__init__.py:97-117)."""
+    metrics.py evaluate back (arguments/__init__.py:97-117).  undistort=True is added only for a run with --undistort, so that
+    surfel_mesh.py -s reloads the same cameras; without the flag the file is what it always was."""
     import argparse
     import os
     os.makedirs(args.model_path, exist_ok=True)
     path = os.path.join(args.model_path, "cfg_args")
     with open(path, "w") as f:
-        f.write(str(argparse.Namespace(**{k: getattr(args, k) for k in _MODEL_ARGS})))
+        cfg = {k: getattr(args, k) for k in _MODEL_ARGS}
+        if getattr(args, "undistort", False):
+            cfg["undistort"] = True
+        f.write(str(argparse.Namespace(**cfg)))
     return path
 
 
@@ -698,7 +704,8 @@ def main(argv=None):
     write_cfg_args(args)
     opt, pipe = optimization_from_args(args), pipeline_params(depth_ratio=args.depth_ratio)
     scene = Scene(args.source_path, args.model_path, images=args.images, resolution=args.resolution, white_background=args.white_background,
-                  eval=args.eval, data_device=args.data_device, seed=args.seed, workers=args.workers, sh_degree=args.sh_degree, decode=args.decode)
+                  eval=args.eval, data_device=args.data_device, seed=args.seed, workers=args.workers, sh_degree=args.sh_degree, decode=args.decode,
+                  undistort=args.undistort)
     model, first_iter = scene.gaussians, 0
     model.training_setup(opt)
     if args.start_checkpoint:
