@@ -49,11 +49,6 @@ __device__ __forceinline__ float row_scan_add_incl(float x) {
     x = row_shr_add<1>(x); x = row_shr_add<2>(x); x = row_shr_add<4>(x); x = row_shr_add<8>(x);
     return x;
 }
-__device__ __forceinline__ float row_scan_add_excl(float x) {
-    float e = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x111, 0xf, 0xf, true));      // row_shr:1, zero fill
-    e = row_shr_add<1>(e); e = row_shr_add<2>(e); e = row_shr_add<4>(e); e = row_shr_add<8>(e);
-    return e;
-}
 
 // index (0 .. 127) of set bit number k (0-based, k < popcount) of the 128-bit word (w1 : w0)
 __device__ __forceinline__ int select_bit128(unsigned long long w0, unsigned long long w1, int k) {
@@ -70,6 +65,47 @@ __device__ __forceinline__ int select_bit128(unsigned long long w0, unsigned lon
     return idx;
 }
 
+// Flush of one round for one (staged instance, record half): NQ float4s of every sub-tile's slot are added into f[], sub-tiles ascending.
+// The slot of sub-tile s is the real one where the instance's rank on list s falls into round c, and a block of zeros (`zs`) otherwise:
+// the accumulators start at +0 and never become -0, so f + (+0) leaves every bit as it is.  No branch, so the loads of FG sub-tiles
+// are issued back to back and the wave waits for one LDS round trip per group instead of one per sub-tile that any of its lanes hits.
+// GUARD (the instrumented instantiations, which spill around their counters): the form with a branch per sub-tile and no zero reads —
+// the same sums, 40 spilled dwords fewer there.
+#ifndef SCAN_FLUSH_GROUP
+#define SCAN_FLUSH_GROUP 4      // 4: 167 / 168 VGPRs, no spills; 2: the same, garden step 3.207 against 3.201 ms; 8 and 16 spill 18 - 102 dwords at the 168-register limit
+#endif
+template <int NQ, int FG, bool GUARD>
+__device__ __forceinline__ void flush_round(const float4* slots, const float4* zs, const uint4 frk, const int c, float4 (&f)[NQ]) {
+    const uint32_t rkw[4] = {frk.x, frk.y, frk.z, frk.w};
+#pragma unroll
+    for (int s0 = 0; s0 < 16; s0 += FG) {
+        float4 v[FG][NQ];
+#pragma unroll
+        for (int j = 0; j < FG; j++) {
+            const int s = s0 + j;
+            const int li = (int)((rkw[s >> 2] >> (8 * (s & 3))) & 0xffu) - CH * c;      // lane of the slot, if this is the rank's round
+            const bool mine = (unsigned)li < (unsigned)CH;                              // (rank 0xff = not on the list: 255 - 16 c >= 143)
+            if (GUARD) {
+                if (mine) {
+#pragma unroll
+                    for (int q = 0; q < NQ; q++) f[q] = add4(f[q], slots[(s * 16 + li) * 5 + q]);
+                }
+            } else {
+                const float4* sp = mine ? slots + (s * 16 + li) * 5 : zs;
+#pragma unroll
+                for (int q = 0; q < NQ; q++) v[j][q] = sp[q];
+            }
+        }
+        if (!GUARD) {
+#pragma unroll
+            for (int j = 0; j < FG; j++) {
+#pragma unroll
+                for (int q = 0; q < NQ; q++) f[q] = add4(f[q], v[j][q]);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // [r6] BATCH TRUNCATION.  A batch lasts (chunks of its longest sub-tile list) rounds, and a round lasts one 16-step walk whatever it
@@ -83,9 +119,6 @@ __device__ __forceinline__ int select_bit128(unsigned long long w0, unsigned lon
 // the chunk" rule; the cost rule above another 0.6 - 0.9 % (r06_ab_scan_trunc_policy.jsonl).
 // (The two staging paths are kept apart with `if constexpr`: an earlier form that shared a lambda between them cost the STREAM
 // instantiation 8 % — same instruction counts, another schedule.)
-#ifndef SCAN_TRUNC_REM
-#define SCAN_TRUNC_REM 1      // 0: fixed 128-position batches
-#endif
 
 // LDS records of a pixel, indexed by the pixel's owner thread (tid = 16 * sub-tile row + pixel of the sub-tile):
 //   s_pix  (read-only in the walk, 3 x float4): [0] gC0 gC1 gC2 g_depth   [1] gN0 gN1 gN2 g_med   [2] a2 a1 a0 last
@@ -97,17 +130,12 @@ __device__ __forceinline__ int select_bit128(unsigned long long w0, unsigned lon
 // every lane — the last lane of a row writes the pixel's state, the others a scratch area behind it — and idle lanes park a
 // (never read) slot as well.
 constexpr int STATE_SCRATCH = 49;      // float4s: 16 steps x 16 B + 64 lanes x 8 B
+constexpr int STATE_ZERO = 3;          // float4s behind the scratch that stay zero: what the flush reads for a slot that is not its instance's
 // The 4 rows of a wave read 4 different pixels' records in one instruction (a broadcast inside each row).  With the natural row
 // strides (16 x 48 B = 192 dwords, 16 x 16 B = 64 dwords: both 0 mod 64 banks) the four addresses fell on the same banks — a 4-way
 // conflict on every read of every step: 16.2 M of the kernel's LDS conflict cycles per launch at C2 against 1.4 M for the rows walk
 // (profiles/r03gscan_C2_pmc.json).  One float4 of padding per row moves the rows 4 banks apart.
 constexpr int PIX_ROW = 16 * 3 + 1, STATE_ROW = 16 + 1;
-#ifndef SCAN_INCL
-#define SCAN_INCL 1      // 1: inclusive sum scan (4 DPP adds) and one subtraction instead of the exclusive one (mov + 4 adds)
-#endif
-#ifndef SCAN_AFFINE
-#define SCAN_AFFINE 1    // 1: the plane gradients are summed as three moments of dL/dp and turned into dL/dTu, dL/dTv, dL/dTw once per chunk
-#endif
 #ifndef SCAN_MIN_WG
 #define SCAN_MIN_WG 3
 #endif
@@ -116,7 +144,7 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
     __shared__ float4 s_rec[SB * 5];                          // 10 KB: q0-q4 of the staged instances
     __shared__ float4 s_slot[BLOCK * 5];                      // 20 KB: the round's partial records, one per walking lane
     __shared__ float4 s_pix[16 * PIX_ROW];                    // 12.3 KB
-    __shared__ float4 s_state[16 * STATE_ROW + STATE_SCRATCH];      // 5.1 KB
+    __shared__ float4 s_state[16 * STATE_ROW + STATE_SCRATCH + STATE_ZERO];      // 5.2 KB
     __shared__ unsigned long long s_bal[16][SB / 64];         // per sub-tile: the staged instances on its list
     __shared__ uint8_t s_list[16][SB];                        // per sub-tile: its list (staged indices, back to front)
     __shared__ uint4 s_rank[SB];                              // per staged instance: its rank on each of the 16 lists (0xff: not on it)
@@ -145,6 +173,7 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
         mine[1] = make_float4(px.gN0, px.gN1, px.gN2, px.g_med);
         mine[2] = make_float4(px.final_A * px.g_dist, -2.f * px.fM1 * px.g_dist, FMA(px.fM2, px.g_dist, px.g_alpha), __int_as_float(px.last));
         s_state[srow * STATE_ROW + i16] = make_float4(px.T, px.X, __int_as_float(px.medc), 0.f);
+        if (tid < STATE_ZERO) s_state[16 * STATE_ROW + STATE_SCRATCH + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
         const int maxc0 = block_max(px.last, &s_max);         // (its barriers also publish s_rowlast and s_pix)
         (void)maxc0;
     }
@@ -169,7 +198,6 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 pa = zero4, pb = zero4, pc = zero4, pd = zero4;
     uint32_t nid = 0;
-    constexpr bool TRUNC = SCAN_TRUNC_REM > 0;
     constexpr bool strm_on = STREAM;      // the host found the forward's tile stream for this frame (surfel_api.hip: stream_lookup)
     const float4* __restrict__ strm = a.strm_rec;
     const uint32_t* __restrict__ smask = a.strm_mask;
@@ -195,7 +223,6 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
             if (a.has_rec && fh == 0) a.has_rec[id] = 1;      // every staged instance gets a record (finish_tail)
             if (fh == 0) { pa = src[0]; pb = src[1]; pc = src[3]; pd = src[4]; } else { pa = src[2]; pb = src[5]; pc = src[6]; }
         }
-        if (!TRUNC && maxc - SB > 0 && ft < min(SB, maxc - SB)) nid = a.point_list[range.x + (maxc - SB - ft) - 1];
     }
     bool pend = false;
     size_t pend_slot = 0;
@@ -241,17 +268,6 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
             else { dst[3] = f0; dst[4] = f1; }
         }
         f0 = zero4; f1 = zero4; f2 = zero4;
-        if (strm_on) {
-            if (!TRUNC && hi - SB > 0) fetch(hi - SB);      // (TRUNC: behind the ballots, once this batch's length is known)
-        } else if (!TRUNC && hi - SB > 0) {   // next batch's records, and the ids of the one behind it
-            const float4* __restrict__ recq = reinterpret_cast<const float4*>(a.rec);
-            if (ft < min(SB, hi - SB)) {
-                const float4* __restrict__ src = recq + (size_t)nid * REC_Q;
-                if (a.has_rec && fh == 0) a.has_rec[nid] = 1;
-                if (fh == 0) { pa = src[0]; pb = src[1]; pc = src[3]; pd = src[4]; } else { pa = src[2]; pb = src[5]; pc = src[6]; }
-            }
-            if (hi - 2 * SB > 0 && ft < min(SB, hi - 2 * SB)) nid = a.point_list[range.x + (hi - 2 * SB - ft) - 1];
-        }
         if (fh == 1) {
 #pragma unroll
             for (int s = 0; s < 16; s++) {
@@ -261,7 +277,7 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
         }
         __syncthreads();
         int keep = mb;                        // staged instances walked in this batch: the deepest `keep`
-        if (TRUNC) {
+        {
             const unsigned long long w0 = s_bal[i16][0], w1 = s_bal[i16][1];
             const int n = __popcll(w0) + __popcll(w1);
             int nm = n;
@@ -341,9 +357,7 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
                 float g[18];
 #pragma unroll
                 for (int v = 0; v < 18; v++) g[v] = 0.f;
-#if SCAN_AFFINE
                 float M1[3] = {0.f, 0.f, 0.f}, M2[3] = {0.f, 0.f, 0.f};      // sums of (pixel column offset) dp and (pixel row offset) dp; g[0..2] holds the sum of dp
-#endif
                 {
                 float4 Sn = srd[0];
                 constexpr float MC1 = FAR_N / (FAR_N - NEAR_N), MC2 = (FAR_N * NEAR_N) / (FAR_N - NEAR_N);
@@ -376,16 +390,10 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
                     u = FMA(depth, A.w, u);
                     u = FMA(q3.x, B.x, u); u = FMA(q3.y, B.y, u); u = FMA(q3.z, B.z, u);
                     const float wu = w * u;
-#if SCAN_INCL
                     const float Xn = S.y + row_scan_add_incl(wu);             // suffix sum from this lane's instance on
                     const float Xb = Xn - wu;                                 // ... and behind it
                     const float dL_dalpha = ok ? FMA(T, u, -(Xb * i1a)) : 0.f;
                     swr[p * 2] = make_float2(T, Xn);
-#else
-                    const float Xb = S.y + row_scan_add_excl(wu);             // suffix sum behind this lane's instance
-                    const float dL_dalpha = ok ? FMA(T, u, -(Xb * i1a)) : 0.f;
-                    swr[p * 2] = make_float2(T, Xb + wu);
-#endif
                     if (STATS) {
                         const unsigned long long okb = __ballot(ok), vb = __ballot(valid);
                         if (lane == 0) {
@@ -405,26 +413,15 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
                     const float g2 = h.use3d ? 0.f : nGG * FILTER_INV_SQUARE;
                     const float ax = FMA(nGG, sxg, dL_dz * Twx) * ipg, ay = FMA(nGG, syg, dL_dz * Twy) * ipg;
                     const float dp2 = -FMA(ax, sxg, ay * syg);
-#if SCAN_AFFINE
                     (void)pxf;
                     g[0] += ax; g[1] += ay; g[2] += dp2;
                     if (ca > 0) { M1[0] = FMA((float)ca, ax, M1[0]); M1[1] = FMA((float)ca, ay, M1[1]); M1[2] = FMA((float)ca, dp2, M1[2]); }
                     if (cb > 0) { M2[0] = FMA((float)cb, ax, M2[0]); M2[1] = FMA((float)cb, ay, M2[1]); M2[2] = FMA((float)cb, dp2, M2[2]); }
                     g[6] = FMA(dL_dz, sxg, g[6]); g[7] = FMA(dL_dz, syg, g[7]); g[8] += dL_dz;
-#else
-                    // -dk = dp x l ,  -dl = k x dp
-                    const float nk0 = FMA(ay, h.lz, -(dp2 * h.ly)), nk1 = FMA(dp2, h.lx, -(ax * h.lz)), nk2 = FMA(ax, h.ly, -(ay * h.lx));
-                    const float nl0 = FMA(h.ky, dp2, -(h.kz * ay)), nl1 = FMA(h.kz, ax, -(h.kx * dp2)), nl2 = FMA(h.kx, ay, -(h.ky * ax));
-                    g[0] += nk0; g[1] += nk1; g[2] += nk2; g[3] += nl0; g[4] += nl1; g[5] += nl2;
-                    g[6] = FMA(dL_dz, sxg, g[6]); g[6] = FMA(-pxf, nk0, g[6]); g[6] = FMA(-pyf, nl0, g[6]);
-                    g[7] = FMA(dL_dz, syg, g[7]); g[7] = FMA(-pxf, nk1, g[7]); g[7] = FMA(-pyf, nl1, g[7]);
-                    g[8] += dL_dz; g[8] = FMA(-pxf, nk2, g[8]); g[8] = FMA(-pyf, nl2, g[8]);
-#endif
                     g[9] = FMA(g2, h.dx, g[9]); g[10] = FMA(g2, h.dy, g[10]);
                 }
                 }
                 }
-#if SCAN_AFFINE
                 {
                     // [r6] per pair  -dk = dp x l  and  -dl = k x dp  with  k = K0 + ca Tw,  l = L0 + cb Tw  (K0, L0: the planes of the sub-tile's first
                     // column / row), so over the chunk's 16 pixels
@@ -461,7 +458,6 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
                     w2 = FMA(-h0.kx, M2[1], w2); w2 = FMA(h0.ky, M2[0], w2);
                     g[0] = u0; g[1] = u1; g[2] = u2; g[3] = v0; g[4] = v1; g[5] = v2; g[6] = w0; g[7] = w1; g[8] = w2;
                 }
-#endif
                 s_slot[tid * 5 + 0] = make_float4(g[0], g[1], g[2], g[3]);
                 s_slot[tid * 5 + 1] = make_float4(g[4], g[5], g[6], g[7]);
                 s_slot[tid * 5 + 2] = make_float4(g[8], g[9], g[10], g[11]);
@@ -475,15 +471,15 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
                 // (the ranks are re-read every round: kept in registers, the compiler hoists sixteen slot addresses per thread out
                 // of the round loop and spills them across the walk)
                 const uint4 frk = s_rank[ft];
-                const uint32_t rkw[4] = {frk.x, frk.y, frk.z, frk.w};
-#pragma unroll
-                for (int s = 0; s < 16; s++) {
-                    const int li = (int)((rkw[s >> 2] >> (8 * (s & 3))) & 0xffu) - CH * c;      // lane of the slot, if this is the rank's round
-                    if ((unsigned)li < (unsigned)CH) {      // (rank 0xff = not on the list: 255 - 16 c >= 143)
-                        const float4* sp = s_slot + (s * 16 + li) * 5;
-                        if (fh == 0) { f0 = add4(f0, sp[0]); f1 = add4(f1, sp[1]); f2 = add4(f2, sp[2]); }
-                        else { f0 = add4(f0, sp[3]); f1 = add4(f1, sp[4]); }
-                    }
+                const float4* const zs = s_state + 16 * STATE_ROW + STATE_SCRATCH;
+                if (fh == 0) {
+                    float4 f[3] = {f0, f1, f2};
+                    flush_round<3, SCAN_FLUSH_GROUP, STATS>(s_slot, zs, frk, c, f);
+                    f0 = f[0]; f1 = f[1]; f2 = f[2];
+                } else {
+                    float4 f[2] = {f0, f1};
+                    flush_round<2, SCAN_FLUSH_GROUP, STATS>(s_slot + 3, zs, frk, c, f);
+                    f0 = f[0]; f1 = f[1];
                 }
             }
             __syncthreads();                  // slots reusable

@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Do two builds of the library give the same BITS?  Every (scene, walk) runs forward + backward under each library in its own
 process (SURFEL_LIB); the gradient tensors' SHA-1 digests are compared.
-    python scripts/lib_identity.py <lib_tag_a> <lib_tag_b> [walk ...]      (tag "-" = the product library; walks: rows quad scan auto)"""
+    python scripts/lib_identity.py <lib_tag_a> <lib_tag_b> [walk ...]      (tag "-" = the product library; walks: rows quad scan auto)
+With SURFEL_IDENTITY_WORKLOADS="garden,C4,..." the frames are a bench workload's instead (helpers_bench: its trainer's first view at its
+initial state, every loss term on): per walk, with the forward's tile stream and with the gathering staging, what the iteration's
+render -> loss -> backward chain hands the optimiser — radii, loss terms, dL/dmeans2D, the gradient store, the colour gradients."""
 import hashlib
 import json
 import os
@@ -39,9 +42,51 @@ def child(walks):
     print("DIGESTS " + json.dumps(out))
 
 
+def _digest(t):
+    """SHA-1 of a device tensor's bits; large tensors through two position-weighted 64-bit sums computed on the device."""
+    import torch
+    b = t.detach().contiguous().view(-1).view(torch.int32)
+    if b.numel() <= 1 << 20:
+        return hashlib.sha1(b.cpu().numpy().tobytes()).hexdigest()
+    w = torch.arange(b.numel(), device=b.device, dtype=torch.int64)
+    x = b.to(torch.int64)
+    sums = [int(x.sum()), int((x * (w % 65521 + 1)).sum()), int((x * (w % 8191 + 1)).sum())]
+    return hashlib.sha1(json.dumps(sums).encode()).hexdigest()
+
+
+def child_workloads(walks, workloads):
+    import torch
+    import surfel_native as n
+    from helpers_bench import TRAINED_PRESETS, make_trainer, trained_trainer
+    import diff_surfel_rasterization as dsr
+    flags = {"rows": n.OPT_BWD_ROWS, "quad": n.OPT_BWD_QUAD, "scan": n.OPT_BWD_SCAN, "auto": 0}
+    dev = torch.device("cuda:0")
+    out = {}
+    for wl in workloads:
+        tr = trained_trainer(dev, wl, "/tmp/state_%s.ply" % wl)[0] if wl in TRAINED_PRESETS else make_trainer(dev, wl, n_views=8)
+        tr._begin_step()
+        cam = tr._next_camera()
+        m = tr.model
+        m.bind(sh_grad=False)
+        for w in walks:
+            for st, gather in (("stream", 0), ("gather", n.OPT_BWD_GATHER)):
+                tr.pipe.debug = flags[w] | gather
+                m.grad.zero_()
+                radii, scalars, g2d = tr._forward_backward(cam, tr.opt.lambda_normal, tr.opt.lambda_dist, False)
+                torch.cuda.synchronize()
+                for k, t in (("radii", radii), ("loss_terms", scalars), ("means2D", g2d), ("grad", m.grad), ("colours", m.gcol)):
+                    out["%s/%s/%s/%s" % (wl, w, st, k)] = _digest(t)
+        tr.pipe.debug = 0
+        del tr, m
+        dsr.set_grad_arena(None)
+        torch.cuda.empty_cache()
+    print("DIGESTS " + json.dumps(out))
+
+
 def main():
     if sys.argv[1] == "--child":
-        return child(sys.argv[2:])
+        wls = os.environ.get("SURFEL_IDENTITY_WORKLOADS")
+        return child_workloads(sys.argv[2:], wls.split(",")) if wls else child(sys.argv[2:])
     tags, walks = sys.argv[1:3], (sys.argv[3:] or ["rows", "scan", "auto"])
     res = []
     for tag in tags:
