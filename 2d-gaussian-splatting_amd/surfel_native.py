@@ -208,6 +208,14 @@ SIGNATURES = {
     "surfel_undistort.h": {
         "surfel_scene_undistort": (_i, _i, _i, _i, _i, _i, _f64p, _f64p, _d, _d, _s),
     },
+    "surfel_log.h": {
+        "surfel_log_append": (_i, _d, _d, _i, _i, _i, _d, _f, _f, _s),
+        "surfel_log_panel": (_i, _i, _i, _i, _d, _d, _d, _i64, _s),
+        "surfel_log_crc32c": (C.c_uint32, _u, _i64),                       # the framing entries take HOST pointers
+        "surfel_log_frame": (_i64, _u, _i64, _u),
+        "surfel_log_steps_capacity": (_i64, _i64),
+        "surfel_log_encode_steps": (_i64, _u, _i64, _f, _f64, _u, _i64),
+    },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
@@ -223,6 +231,7 @@ JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])
 UNDISTORT_EXPORTS = list(SIGNATURES["surfel_undistort.h"])
+LOG_EXPORTS = list(SIGNATURES["surfel_log.h"])
 _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items()}
 
 

@@ -139,7 +139,7 @@ def capture_views(gt_model, cams, background, pipe=None):
 # ------------------------------------------------------------------------------------------------ the loop
 class Trainer:
     def __init__(self, model, cams, opt=None, pipe=None, white_background=False, extent=None, seed=0, sharding="views", first_iter=0,
-                 rehearse_exchange=False, solo=False):
+                 rehearse_exchange=False, solo=False, logger=None):
         """sharding (N > 1): "views" = every rank trains on its own view per step (default, BASELINE config 4); "bands" = all ranks
         render row bands of the SAME view (tile-band sharding, BASELINE config 5): every rank evaluates the loss on ITS band plus a
         32-row halo received from its two neighbours (surfel_losses.train_loss_band), back-propagates its own rows, and the
@@ -149,7 +149,9 @@ class Trainer:
         rehearse_exchange: take the view-parallel step (schedule, collectives, split optimiser) even with a single rank — the
         N > 1 code path run against the real backend on one GPU (tests/test_gpu_train.py, scripts/rccl_selfcheck.py).
         solo: ignore an initialised process group — this rank trains alone (bench.py: every rank prepares the same trained state by
-        itself, deterministically, before the timed view-parallel Trainer synchronises the replicas)."""
+        itself, deterministically, before the timed view-parallel Trainer synchronises the replicas).
+        logger: a surfel_log.EventWriter (LOG.md): rank 0 appends every step's scalars to it with one launch behind the step's work; None
+        (the default): no launch, no buffer, no thread."""
         if sharding not in ("views", "bands"):
             raise ValueError("sharding must be 'views' or 'bands'")
         self.sharding = sharding
@@ -166,6 +168,8 @@ class Trainer:
         self._stack = []
         self.iteration = int(first_iter)      # resume: the checkpoint's iteration (train.py:37-39), so that the lr / SH / densify schedules continue
         self.last = {}
+        self.logger = logger
+        self._lambdas = (0.0, 0.0)
         self._epoch, self._epoch_views, self._epoch_campos, self._centers = -1, None, None, None
         self._one = torch.ones((), dtype=torch.float32, device=model.device)
         # test handles (tests/test_gpu_train.py compares each with its bit-identical alternative)
@@ -247,14 +251,19 @@ class Trainer:
     def step(self):
         """One training iteration (train.py:54-138).  Returns nothing; `self.last` holds device scalars for logging."""
         if self.world == 1 and self.views_per_step > 1:
-            return self._step_accumulate(self.views_per_step)
-        it, lam_n, lam_d = self._begin_step()
-        cam = self._next_camera()
-        self.model.bind(sh_grad=False)      # the SH gradients are rebuilt inside the optimiser kernel from the colour gradients
-        if self.world > 1 and self.sharding == "bands":
-            self._step_band(it, cam, lam_n, lam_d)
+            self._step_accumulate(self.views_per_step)
         else:
-            self._step_view(it, cam, lam_n, lam_d)
+            it, lam_n, lam_d = self._begin_step()
+            cam = self._next_camera()
+            self.model.bind(sh_grad=False)      # the SH gradients are rebuilt inside the optimiser kernel from the colour gradients
+            if self.world > 1 and self.sharding == "bands":
+                self._step_band(it, cam, lam_n, lam_d)
+            else:
+                self._step_view(it, cam, lam_n, lam_d)
+        if self.logger is not None and self.rank == 0:
+            # the step's work is queued: the deferred loss scalars are valid on the stream, and `points` is the count the step rendered
+            # (training_report runs before the densification, train.py:119-132)
+            self.logger.append(self.iteration, self.last["points"], self.last["scalars"], *self._lambdas)
 
     def _begin_step(self):
         """Advance the iteration, set its learning rate and SH degree; returns (iteration, lambda_normal, lambda_dist)."""
@@ -263,7 +272,8 @@ class Trainer:
         self.model.update_learning_rate(it)
         if it % getattr(opt, "sh_degree_interval", 1000) == 0:
             self.model.oneupSHdegree()
-        return it, (opt.lambda_normal if it > opt.normal_from_iter else 0.0), (opt.lambda_dist if it > opt.dist_from_iter else 0.0)
+        self._lambdas = ((opt.lambda_normal if it > opt.normal_from_iter else 0.0), (opt.lambda_dist if it > opt.dist_from_iter else 0.0))
+        return (it,) + self._lambdas
 
     def _step_view(self, it, cam, lam_n, lam_d):
         """One GPU, or view-parallel (N ranks, or the world-1 rehearsal): every rank trains on its own view."""
@@ -609,13 +619,14 @@ _OPTIMIZATION_ARGS = ("iterations", "position_lr_init", "position_lr_final", "po
 
 
 def parse_args(argv=None):
-    """The reference's flags with its defaults (arguments/__init__.py:47-95, train.py:258-265), without the viewer's --ip / --port:
-    those are parse_viewer_args', which main() lets take its two flags out of the command line first."""
+    """The reference's flags with its defaults (arguments/__init__.py:47-95, train.py:258-265), without the viewer's --ip / --port and
+    the log's --tensorboard: those are parse_viewer_args', which main() lets take its flags out of the command line first."""
     import argparse
     import os
     ap = argparse.ArgumentParser(description="Train a 2-D Gaussian surfel model on a COLMAP or Blender capture",
                                  epilog="The remote viewer (VIEWER.md): --port PORT serves it while training, on --ip IP (default 127.0.0.1); "
-                                        "without --port no listener exists.")
+                                        "without --port no listener exists.  --tensorboard writes a TensorBoard event file into the "
+                                        "model folder (LOG.md); without it nothing is logged.")
     g = ap.add_argument_group("Loading Parameters")
     g.add_argument("--source_path", "-s", default="", type=str)
     g.add_argument("--model_path", "-m", default="", type=str)
@@ -676,6 +687,8 @@ def parse_viewer_args(argv=None):
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--ip", type=str, default="127.0.0.1", help="address the remote viewer's listener binds (with --port)")
     ap.add_argument("--port", type=int, default=None, help="serve the SIBR remote viewer on this port while training (default: no listener)")
+    ap.add_argument("--tensorboard", action="store_true", help="write the reference's TensorBoard log (scalars per step, image panels at the "
+                    "test iterations) as an event file into the model folder (LOG.md; default: no log)")
     return ap.parse_known_args(argv)
 
 
@@ -685,6 +698,14 @@ def make_viewer(vargs):
         return None
     import surfel_view
     return surfel_view.Viewer(vargs.ip, vargs.port)
+
+
+def make_logger(vargs, model_path):
+    """The event writer for --tensorboard, or None: without the flag no file, thread or buffer is created."""
+    if not getattr(vargs, "tensorboard", False):
+        return None
+    import surfel_log
+    return surfel_log.EventWriter(model_path)
 
 
 def main(argv=None):
@@ -711,11 +732,15 @@ def main(argv=None):
     if args.start_checkpoint:
         model_params, first_iter = torch.load(args.start_checkpoint, weights_only=False)
         model.restore(model_params, opt)
-    tr = Trainer(model, scene.getTrainCameras(), opt, pipe, args.white_background, extent=scene.cameras_extent, seed=args.seed, first_iter=first_iter)
+    logger = make_logger(vargs, args.model_path)
+    tr = Trainer(model, scene.getTrainCameras(), opt, pipe, args.white_background, extent=scene.cameras_extent, seed=args.seed, first_iter=first_iter,
+                 logger=logger)
     train_cams = scene.getTrainCameras()
     reports = (("test", scene.getTestCameras()), ("train", [train_cams[i % len(train_cams)] for i in range(5, 30, 5)]))
     viewer = make_viewer(vargs)
     t0 = time.perf_counter()
+    if logger is not None:
+        logger.mark()      # iter_time of the first block counts from here, not from the writer's creation
     while tr.iteration < opt.iterations:
         tr.step()
         it = tr.iteration
@@ -724,7 +749,11 @@ def main(argv=None):
         if it in args.test_iterations:
             for name, cams in reports:
                 if cams:
-                    ps, l1 = tr.evaluate(cams)
+                    if logger is not None:      # the same evaluation, with its numbers and the views' panels logged (LOG.md)
+                        import surfel_log
+                        ps, l1 = surfel_log.report(tr, logger, name, cams, first=it == args.test_iterations[0])
+                    else:
+                        ps, l1 = tr.evaluate(cams)
                     say("\n[ITER {}] Evaluating {}: L1 {} PSNR {}".format(it, name, l1, ps))
         if it in args.save_iterations:
             say("\n[ITER {}] Saving Gaussians".format(it))
@@ -734,6 +763,8 @@ def main(argv=None):
             torch.save((model.capture(), it), os.path.join(args.model_path, "chkpnt" + str(it) + ".pth"))
     if viewer is not None:
         viewer.close()
+    if logger is not None:
+        logger.close()
     torch.cuda.synchronize()
     say("\nTraining complete: %d iterations, %d points, %.1f s." % (tr.iteration - first_iter, model.P, time.perf_counter() - t0))
     return 0
