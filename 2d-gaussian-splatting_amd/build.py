@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsurfel_hip.so")
 SOURCES = ["surfel_preprocess.hip", "surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_sort.hip", "surfel_api.hip", "knn.hip", "box_probe.hip",
            "train_loss.hip", "train_post.hip", "train_fused.hip", "train_optim.hip", "train_api.hip",
-           "device_scan.hip", "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "frame_jpeg.hip", "frame_png.hip", "scene_jpeg.hip", "scene_undistort.hip", "train_log.hip", "log_events.cpp"]
+           "device_scan.hip", "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "mesh_view.hip", "frame_jpeg.hip", "frame_png.hip", "scene_jpeg.hip", "scene_undistort.hip", "train_log.hip", "log_events.cpp"]
 # blend kernels: packed-f32 VALU (SLP) costs ~1.6x a scalar op on gfx950 plus the v_movs that pair the operands
 # surfel_backward.hip spells every fused multiply-add out (FMA macro) and is compiled with contraction off, so its kernel variants
 # round identically per (pixel, surfel) pair
@@ -36,6 +36,9 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          # mesh_cull.hip: no contraction, so the visibility kernel's fp32 chain rounds as its restatement (tests/cull_oracle.py); the
          # rasteriser writes its fused multiply-adds out
          "mesh_cull.hip": ["-ffp-contract=off"],
+         # mesh_view.hip: no contraction, so the vertex-normal and shading kernels (fp32) round as their restatement
+         # (tests/meshview_oracle.py); the rasteriser it shares with mesh_cull.hip (mesh_raster.h) writes its fused multiply-adds out
+         "mesh_view.hip": ["-ffp-contract=off"],
          # frame_jpeg.hip: no contraction, so the colour conversion, the DCT sums and the quantiser's division (fp32) round as their
          # restatement (tests/video_oracle.py) and the JPEG file comes out byte for byte
          "frame_jpeg.hip": ["-ffp-contract=off"],
@@ -53,7 +56,8 @@ HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_blend_bwd.h", "train_k
            "vis_pixels.h", os.path.join("..", "..", "include", "surfel_view.h"), os.path.join("..", "..", "include", "surfel_cull.h"),
            "jpeg_tables.h", os.path.join("..", "..", "include", "surfel_jpeg.h"), os.path.join("..", "..", "include", "surfel_png.h"),
            os.path.join("..", "..", "include", "surfel_jpegdec.h"), os.path.join("..", "..", "include", "surfel_undistort.h"),
-           "log_jet_table.h", os.path.join("..", "..", "include", "surfel_log.h")]
+           "log_jet_table.h", os.path.join("..", "..", "include", "surfel_log.h"), "mesh_raster.h",
+           os.path.join("..", "..", "include", "surfel_meshview.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-result"]
 
 

@@ -15,14 +15,6 @@ namespace surfel {
 constexpr int VT = 256;      // threads per workgroup
 constexpr int NR = SURFEL_VIS_MAX_RANKS;
 
-// save_img_u8's arithmetic on one value (fp32, one rounding per operation)
-__device__ __forceinline__ uint32_t quant8(float v, float scale, float bias) {
-    float y = __fadd_rn(__fmul_rn(v, scale), bias);
-    if (y != y) y = 0.0f;                      // nan_to_num: NaN -> 0 (+-inf -> +-FLT_MAX, which the clip treats as it treats +-inf)
-    y = y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
-    return (uint32_t)(int)__fmul_rn(y, 255.0f);
-}
-
 template <int C>
 __global__ void __launch_bounds__(VT) vis_quantize_kernel(int64_t hw, const float* __restrict__ planes, float scale, float bias, uint8_t* __restrict__ dst) {
     const int64_t i = ((int64_t)blockIdx.x * VT + threadIdx.x) * PX;

@@ -8,6 +8,14 @@ namespace surfel {
 
 constexpr int PX = 4;        // consecutive pixels per lane: 16 B of every plane in, 4 C bytes out
 
+// save_img_u8's arithmetic on one value (fp32, one rounding per operation); also the quantiser of the mesh viewer's shading (mesh_view.hip)
+__device__ __forceinline__ uint32_t quant8(float v, float scale, float bias) {
+    float y = __fadd_rn(__fmul_rn(v, scale), bias);
+    if (y != y) y = 0.0f;                      // nan_to_num: NaN -> 0 (+-inf -> +-FLT_MAX, which the clip treats as it treats +-inf)
+    y = y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
+    return (uint32_t)(int)__fmul_rn(y, 255.0f);
+}
+
 // ---- 4 pixels in, 4 C bytes out --------------------------------------------------------------------------------------------------------
 // v[0..3] <- p[i .. i + 3]: one 16-byte load where the address allows it (the same answer for every lane of a plane: lanes are 16 B
 // apart), four 4-byte loads otherwise; nothing at or behind p[n] is read

@@ -472,6 +472,11 @@ def build_parser():
     ap.add_argument("--fps", default=60, type=int, help="Path: frame rate of the videos")
     ap.add_argument("--png", default="pillow", choices=["pillow", "device"], help="who encodes the PNG files of --render_path and of the renders / gt "
                     "export: Pillow on host threads (the default) or the encoder on the device (PNG.md); the same names and pixels")
+    ap.add_argument("--render_mesh", action="store_true", help="Path: with --render_path, also fly the same path around the mesh this run writes "
+                    "(with --skip_mesh: around the existing fuse_post.ply / fuse_unbounded_post.ply) into MODEL/traj/ours_N/mesh/ (MESHVIEW.md)")
+    ap.add_argument("--mesh_modes", nargs="+", default=["shaded", "normal"], choices=["shaded", "normal", "color", "depth"],
+                    help="Path: the frame sets of --render_mesh: mesh/{mode}_%%05d.png, and render_traj_mesh_{mode}.avi with --video")
+    ap.add_argument("--mesh_ssaa", default=2, type=int, choices=[1, 2, 3, 4], help="Path: samples per pixel edge of --render_mesh")
     ap.add_argument("--decode", default="host", choices=["host", "device"], help="with -s: who decodes the capture's JPEG files: Pillow on the host "
                     "(the default) or the decoder on the device (JPEGDEC.md); the same cameras")
     return ap
@@ -519,7 +524,19 @@ def main(argv=None):
         surfel_path.render_path(gaussians, cams, render, pipe, ext.background, traj_dir, n_frames=args.n_frames, vis_normals=args.vis_normals,
                                 **path_video_args(args), **path_png_args(args))
         print("trajectory frames saved at {}".format(traj_dir))
+    post_name = "fuse_unbounded_post.ply" if args.unbounded else "fuse_post.ply"
+
+    def render_mesh_path(mesh):
+        """--render_path --render_mesh: the path of the surfels' fly-through around the mesh, beside traj/ours_N/renders"""
+        import surfel_meshview
+        surfel_meshview.render_mesh_path(mesh, cams, traj_dir, n_frames=args.n_frames, modes=tuple(args.mesh_modes), ssaa=args.mesh_ssaa,
+                                         **path_video_args(args), **path_png_args(args))
+        print("mesh trajectory frames saved at {}".format(os.path.join(traj_dir, "mesh")))
+
     if args.skip_mesh:
+        if args.render_path and args.render_mesh:
+            v, t, c = surfel_io.read_triangle_mesh(os.path.join(out, post_name))
+            render_mesh_path(TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev)))
         return 0
     gaussians.active_sh_degree = 0      # render.py:91: diffuse colour only
     ext.reconstruction(cams)
@@ -537,6 +554,8 @@ def main(argv=None):
     post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
     surfel_io.write_triangle_mesh(os.path.join(out, name.replace(".ply", "_post.ply")), post)
     print("mesh post processed saved at {}".format(os.path.join(out, name.replace(".ply", "_post.ply"))))
+    if args.render_path and args.render_mesh:
+        render_mesh_path(post)
     return 0
 
 

@@ -191,6 +191,11 @@ SIGNATURES = {
         "surfel_cull_mesh_depth": (_i64, _a, _u, _i64, _i64, _d, _d, _i, _d, _d, _i, _i, _i, _f, _f, _i, _d, _fp, _s),
         "surfel_cull_visibility": (_i, _i64, _d, _i, _d, _d, _i, _i, _i, _d, _f, _d, _s),
     },
+    "surfel_meshview.h": {
+        "surfel_meshview_visibility": (_i64, _a, _u, _i64, _i64, _d, _d, _i, _d, _d, _i, _i, _i, _f, _f, _i, _d, _fp, _s),
+        "surfel_meshview_vertex_normals": (_i, _i64, _i64, _d, _d, _d, _d, _s),
+        "surfel_meshview_shade": (_i, _i64, _i64, _d, _d, _d, _d, _i, _d, _d, _i, _i, _i, _i, _d, _i, _f, _f, _f, _d, _s),
+    },
     "surfel_jpeg.h": {
         "surfel_jpeg_capacity": (_i64, _i, _i),
         "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
@@ -227,6 +232,7 @@ SCENE_EXPORTS = list(SIGNATURES["surfel_scene.h"])
 VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
 VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
+MESHVIEW_EXPORTS = list(SIGNATURES["surfel_meshview.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])

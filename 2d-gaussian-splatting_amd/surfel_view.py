@@ -7,7 +7,7 @@ include/surfel_vis.h) that turn the render package into the interleaved bytes of
 never leaving the device — one non-blocking copy into a pinned buffer that is reused from frame to frame, one event wait, and the
 socket.  The protocol is host code.
 
-    python surfel_view.py -m MODEL [-s CAPTURE] [--iteration N] [--ip 127.0.0.1] [--port 6009]
+    python surfel_view.py -m MODEL [-s CAPTURE] [--iteration N] [--ip 127.0.0.1] [--port 6009] [--mesh MESH.ply]
 """
 import json
 import os
@@ -23,6 +23,7 @@ import surfel_path as _sp
 _n.load()
 
 RENDER_ITEMS = ["RGB", "Alpha", "Normal", "Depth", "Edge", "Curvature"]      # arguments/__init__.py:57, the order the viewer's menu indexes
+MESH_ITEMS = {"Mesh": "shaded", "Mesh Normal": "normal"}      # appended to the menu of a Viewer that was given a mesh (MESHVIEW.md)
 DEFAULT_TIMEOUT = 5.0      # seconds a connected viewer may stay silent (or not read) before it is dropped
 
 
@@ -167,8 +168,11 @@ class Viewer:
     """The listener (None for a Viewer attached to a socket that is connected already) and the one connection.  serve() is what a
     training loop calls after every step, and what the stand-alone viewer calls forever."""
 
-    def __init__(self, host="127.0.0.1", port=6009, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, listener=True):
+    def __init__(self, host="127.0.0.1", port=6009, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, listener=True, mesh=None):
         self.timeout, self.device, self.items = timeout, device, list(items)
+        self.mesh, self._mesh_normals = mesh, None      # a surfel_mesh.TriangleMesh on the device: two more items, served by surfel_meshview
+        if mesh is not None:
+            self.items += list(MESH_ITEMS)
         self.listener = open_listener(host, port) if listener else None
         self.conn = None
         self.frames = 0
@@ -176,9 +180,9 @@ class Viewer:
         self._event = None
 
     @classmethod
-    def attached(cls, sock, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS):
+    def attached(cls, sock, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, mesh=None):
         """A Viewer on a connected socket object (one end of a socketpair, an accepted connection): no listener, nothing is bound."""
-        v = cls(timeout=timeout, device=device, items=items, listener=False)
+        v = cls(timeout=timeout, device=device, items=items, listener=False, mesh=mesh)
         v._adopt(sock)
         return v
 
@@ -225,6 +229,22 @@ class Viewer:
         self._event.synchronize()
         return memoryview(host.numpy())
 
+    def _mesh_mode(self, render_mode):
+        """the surfel_meshview mode of a menu entry that shows the mesh (an index into this viewer's items, or a name); None for the others"""
+        if self.mesh is None:
+            return None
+        if isinstance(render_mode, str):
+            return next((m for name, m in MESH_ITEMS.items() if name.lower() == render_mode.lower()), None)
+        first = len(self.items) - len(MESH_ITEMS)      # (the mesh items are the last ones of the menu)
+        return MESH_ITEMS[self.items[render_mode]] if first <= render_mode < len(self.items) else None
+
+    def _mesh_image(self, cam, mode):
+        """uint8 [H, W, 3] on the device: the mesh for the viewer's camera, one sample per pixel, on white (surfel_meshview.render_mesh)"""
+        import surfel_meshview
+        if self._mesh_normals is None:
+            self._mesh_normals = surfel_meshview.vertex_normals(self.mesh)
+        return surfel_meshview.render_mesh(self.mesh, [cam], mode=mode, ssaa=1, normals=self._mesh_normals)[0]
+
     @torch.no_grad()
     def serve(self, gaussians, pipe, background, source_path="", metrics_fn=None, iteration=0, iterations=0):
         """train.py:146-168.  Without a connection: one accept attempt, and back.  With one: answer the viewer's messages — render its
@@ -239,8 +259,12 @@ class Viewer:
                 image_bytes = None
                 cam, do_training, keep_alive, scaling_modifier, render_mode = self.conn.receive()
                 if cam is not None:
-                    pkg = render(cam, gaussians, pipe, background, scaling_modifier)
-                    image_bytes = self._to_host(net_image(pkg, render_mode))
+                    mesh_mode = self._mesh_mode(render_mode)
+                    if mesh_mode is not None:
+                        image_bytes = self._to_host(self._mesh_image(cam, mesh_mode))
+                    else:
+                        pkg = render(cam, gaussians, pipe, background, scaling_modifier)
+                        image_bytes = self._to_host(net_image(pkg, render_mode))
                     self.frames += 1
                 self.conn.send(image_bytes, source_path, metrics_fn() if metrics_fn is not None else {})
                 if do_training and (iteration < int(iterations) or not keep_alive):
@@ -260,6 +284,7 @@ def build_parser():
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--ip", type=str, default="127.0.0.1")
     ap.add_argument("--port", type=int, default=6009)
+    ap.add_argument("--mesh", type=str, default=None, help="a mesh (.ply) to show as two more menu items, Mesh and Mesh Normal (MESHVIEW.md)")
     return ap
 
 
@@ -281,7 +306,12 @@ def main(argv=None):
     pipe = argparse.Namespace(depth_ratio=args.depth_ratio, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
     background = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
     print("View: " + args.model_path)
-    viewer = Viewer(args.ip, args.port)
+    mesh = None
+    if args.mesh is not None:
+        import surfel_io
+        from surfel_mesh import TriangleMesh
+        mesh = TriangleMesh(*(torch.from_numpy(a).to(dev) for a in surfel_io.read_triangle_mesh(args.mesh)))
+    viewer = Viewer(args.ip, args.port, mesh=mesh)
     metrics = {"#": int(gaussians.get_opacity.shape[0])}
     try:
         while True:      # (train = 0 keeps serve() inside; a dropped viewer brings it back here to wait for the next one)
