@@ -479,6 +479,10 @@ def build_parser():
     ap.add_argument("--mesh_ssaa", default=2, type=int, choices=[1, 2, 3, 4], help="Path: samples per pixel edge of --render_mesh")
     ap.add_argument("--decode", default="host", choices=["host", "device"], help="with -s: who decodes the capture's JPEG files: Pillow on the host "
                     "(the default) or the decoder on the device (JPEGDEC.md); the same cameras")
+    ap.add_argument("--simplify_cell", default=None, type=float, help="Mesh: also write fuse_post_simplified.ply (fuse_unbounded_post_simplified.ply), "
+                    "the post-processed mesh clustered on a grid of this many voxels per cell (SIMPLIFY.md)")
+    ap.add_argument("--simplify_faces", default=None, type=int, help="Mesh: the same file, with the grid chosen so that at most this many triangles "
+                    "remain")
     return ap
 
 
@@ -496,6 +500,10 @@ def path_png_args(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.simplify_cell is not None and args.simplify_faces is not None:
+        raise SystemExit("give --simplify_cell or --simplify_faces, not both")
+    if args.simplify_cell is not None and not args.simplify_cell > 0:
+        raise SystemExit("--simplify_cell must be positive")
     import surfel_io
     import surfel_model
     from surfel_render import render
@@ -543,6 +551,7 @@ def main(argv=None):
     if args.unbounded:
         name = "fuse_unbounded.ply"
         mesh = ext.extract_mesh_unbounded(resolution=args.mesh_res)
+        voxel_size = ext.radius * 2 / args.mesh_res      # (the unbounded lattice's voxel near the centre)
     else:
         name = "fuse.ply"
         depth_trunc = ext.radius * 2.0 if args.depth_trunc < 0 else args.depth_trunc
@@ -554,6 +563,14 @@ def main(argv=None):
     post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
     surfel_io.write_triangle_mesh(os.path.join(out, name.replace(".ply", "_post.ply")), post)
     print("mesh post processed saved at {}".format(os.path.join(out, name.replace(".ply", "_post.ply"))))
+    if args.simplify_cell is not None or args.simplify_faces is not None:
+        import surfel_simplify
+        cell = None if args.simplify_cell is None else args.simplify_cell * voxel_size
+        simple, stats = surfel_simplify.simplify_mesh(post, cell=cell, target_faces=args.simplify_faces)
+        simple_path = os.path.join(out, name.replace(".ply", "_post_simplified.ply"))
+        surfel_io.write_triangle_mesh(simple_path, simple)
+        print("mesh simplified ({} of {} triangles, cell {:g}) saved at {}".format(simple.triangles.shape[0], post.triangles.shape[0], stats["cell"],
+                                                                                  simple_path))
     if args.render_path and args.render_mesh:
         render_mesh_path(post)
     return 0

@@ -196,6 +196,12 @@ SIGNATURES = {
         "surfel_meshview_vertex_normals": (_i, _i64, _i64, _d, _d, _d, _d, _s),
         "surfel_meshview_shade": (_i, _i64, _i64, _d, _d, _d, _d, _i, _d, _d, _i, _i, _i, _i, _d, _i, _f, _f, _f, _d, _s),
     },
+    "surfel_simplify.h": {
+        "surfel_simplify_bounds": (_i, _a, _u, _i64, _d, _fp, _s),                       # bounds, origin, counts, stage_ms: HOST pointers
+        "surfel_simplify_clusters": (_i64, _a, _u, _i64, _d, _fp, _fp, _f, _d, _s),
+        "surfel_simplify_count": (_i64, _a, _u, _i64, _i64, _d, _d, _fp, _fp, _f, _i64p, _s),
+        "surfel_simplify_mesh": (_i, _a, _u, _i64, _i64, _d, _d, _d, _fp, _fp, _f, _f64, _d, _d, _d, _d, _d, _i64p, _fp, _s),
+    },
     "surfel_jpeg.h": {
         "surfel_jpeg_capacity": (_i64, _i, _i),
         "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
@@ -233,6 +239,7 @@ VIS_EXPORTS = list(SIGNATURES["surfel_vis.h"])
 VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 MESHVIEW_EXPORTS = list(SIGNATURES["surfel_meshview.h"])
+SIMPLIFY_EXPORTS = list(SIGNATURES["surfel_simplify.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])
