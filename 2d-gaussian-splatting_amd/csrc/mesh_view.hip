@@ -8,6 +8,7 @@
 
 #include "../../include/surfel_meshview.h"
 #include "mesh_raster.h"
+#include "mesh_sample.h"
 #include "side_util.h"
 #include "vis_pixels.h"
 
@@ -59,41 +60,17 @@ __global__ void __launch_bounds__(CT) meshview_vertex_normals_kernel(int64_t V, 
 // ---- shading ----------------------------------------------------------------------------------------------------------------------------
 struct MvColor { float r, g, b; };
 
-// One sample of the visibility buffer (MESHVIEW.md §Shading, the numbered steps).  x, y: the sample's integer coordinates in the
-// sample grid whose intrinsics the camera holds.
+// One sample of the visibility buffer (MESHVIEW.md §Shading, the numbered steps; steps 1 to 4 are mesh_sample.h's).  x, y: the sample's
+// integer coordinates in the sample grid whose intrinsics the camera holds.
 __device__ inline MvColor meshview_sample(uint64_t key, float x, float y, const CullCam& c, int64_t V, int64_t F, const float* __restrict__ verts,
                                           const int32_t* __restrict__ tris, const float* __restrict__ colors, const float* __restrict__ normals, int mode,
                                           MvColor bg) {
-    const uint32_t t = (uint32_t)key;
-    if ((uint32_t)(key >> 32) >= CULL_INF || (int64_t)t >= F) return bg;
-    const int64_t i0 = tris[3 * (int64_t)t], i1 = tris[3 * (int64_t)t + 1], i2 = tris[3 * (int64_t)t + 2];
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) return bg;
-    const float px0 = verts[3 * i0], py0 = verts[3 * i0 + 1], pz0 = verts[3 * i0 + 2];
-    const float px1 = verts[3 * i1], py1 = verts[3 * i1 + 1], pz1 = verts[3 * i1 + 2];
-    const float px2 = verts[3 * i2], py2 = verts[3 * i2 + 1], pz2 = verts[3 * i2 + 2];
+    MeshSample sm;
+    if (!mesh_sample(key, x, y, c, V, F, verts, tris, sm)) return bg;      // steps 1 to 4 (mesh_sample.h)
+    const int64_t i0 = sm.i0, i1 = sm.i1, i2 = sm.i2;
     const float* m = c.m;
-    // 1: camera space (CULL.md rule 1)
-    const float X0 = ((m[0] * px0 + m[1] * py0) + m[2] * pz0) + m[3], Y0 = ((m[4] * px0 + m[5] * py0) + m[6] * pz0) + m[7],
-                Z0 = ((m[8] * px0 + m[9] * py0) + m[10] * pz0) + m[11];
-    const float X1 = ((m[0] * px1 + m[1] * py1) + m[2] * pz1) + m[3], Y1 = ((m[4] * px1 + m[5] * py1) + m[6] * pz1) + m[7],
-                Z1 = ((m[8] * px1 + m[9] * py1) + m[10] * pz1) + m[11];
-    const float X2 = ((m[0] * px2 + m[1] * py2) + m[2] * pz2) + m[3], Y2 = ((m[4] * px2 + m[5] * py2) + m[6] * pz2) + m[7],
-                Z2 = ((m[8] * px2 + m[9] * py2) + m[10] * pz2) + m[11];
-    // 2: n0 = v1 x v2, n1 = v2 x v0, n2 = v0 x v1, det, its sign
-    const float n0x = Y1 * Z2 - Z1 * Y2, n0y = Z1 * X2 - X1 * Z2, n0z = X1 * Y2 - Y1 * X2;
-    const float n1x = Y2 * Z0 - Z2 * Y0, n1y = Z2 * X0 - X2 * Z0, n1z = X2 * Y0 - Y2 * X0;
-    const float n2x = Y0 * Z1 - Z0 * Y1, n2y = Z0 * X1 - X0 * Z1, n2z = X0 * Y1 - Y0 * X1;
-    const float det = (X0 * n0x + Y0 * n0y) + Z0 * n0z;
-    const float sg = det < 0.0f ? -1.0f : 1.0f;
-    // 3: the ray and the edge values in the plain form
-    const float dx = (x - c.cx) / c.fx, dy = (y - c.cy) / c.fy;
-    const float e0 = sg * ((n0x * dx + n0y * dy) + n0z), e1 = sg * ((n1x * dx + n1y * dy) + n1z), e2 = sg * ((n2x * dx + n2y * dy) + n2z);
-    // 4: clamped weights
-    const float w0 = e0 > 0.0f ? e0 : 0.0f, w1 = e1 > 0.0f ? e1 : 0.0f, w2 = e2 > 0.0f ? e2 : 0.0f;
-    const float ws = (w0 + w1) + w2;
-    const float third = 1.0f / 3.0f;
-    const bool some = ws > 0.0f;
-    const float l0 = some ? w0 / ws : third, l1 = some ? w1 / ws : third, l2 = some ? w2 / ws : third;
+    const float n0x = sm.n0x, n0y = sm.n0y, n0z = sm.n0z, n1x = sm.n1x, n1y = sm.n1y, n1z = sm.n1z, n2x = sm.n2x, n2y = sm.n2y, n2z = sm.n2z;
+    const float dx = sm.dx, dy = sm.dy, l0 = sm.l0, l1 = sm.l1, l2 = sm.l2;
     // 5: the face normal in camera space, against the ray
     float fx = (n0x + n1x) + n2x, fy = (n0y + n1y) + n2y, fz = (n0z + n1z) + n2z;
     const float flen = sqrtf((fx * fx + fy * fy) + fz * fz);

@@ -2,6 +2,8 @@
 scene/gaussian_model.py:193-207 writes it through plyfile (binary little-endian, one `vertex` element, float32
 properties x,y,z,nx,ny,nz,f_dc_*,f_rest_*,opacity,scale_*,rot_*) and as :214-255 reads it back.  numpy only.
 """
+import os
+
 import numpy as np
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
@@ -144,6 +146,74 @@ def read_triangle_mesh(path):
     if tris is None:
         tris = np.zeros((0, 3), np.int32)
     return verts, tris, cols
+
+
+def write_obj(path, vertices, triangles, vt=None, texture=None):
+    """Wavefront OBJ of a mesh (numpy arrays or tensors): `v x y z` per vertex, `f a b c` per triangle (1-based).  vt [F, 3, 2]: three
+    texture coordinates per triangle in OBJ's convention (the origin at the image's lower left corner), written as 3 F `vt u v` lines
+    and `f a/ta b/tb c/tc`.  texture: the image's file name; a material library beside the OBJ (the same name with .mtl) names it."""
+    def host(x):
+        return np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x)
+    v = host(vertices).astype(np.float32).reshape(-1, 3)
+    f = host(triangles).astype(np.int64).reshape(-1, 3)
+    lines = []
+    if texture is not None:
+        mtl = os.path.splitext(os.path.basename(path))[0] + ".mtl"
+        with open(os.path.join(os.path.dirname(path), mtl), "w") as fh:
+            fh.write("newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s\n" % texture)
+        lines += ["mtllib %s" % mtl, "usemtl atlas"]
+    lines += ["v %.9g %.9g %.9g" % tuple(p) for p in v.tolist()]
+    if vt is None:
+        lines += ["f %d %d %d" % (a + 1, b + 1, c + 1) for a, b, c in f.tolist()]
+    else:
+        t = host(vt).astype(np.float32).reshape(-1, 2)
+        if len(t) != 3 * len(f):
+            raise ValueError("write_obj: %d texture coordinates for %d triangles" % (len(t), len(f)))
+        lines += ["vt %.9g %.9g" % tuple(q) for q in t.tolist()]
+        lines += ["f %d/%d %d/%d %d/%d" % (a + 1, 3 * k + 1, b + 1, 3 * k + 2, c + 1, 3 * k + 3) for k, (a, b, c) in enumerate(f.tolist())]
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_obj(path):
+    """(vertices [V, 3] float32, triangles [F, 3] int32, vt [F, 3, 2] float32 or None, texture file name or None) of an OBJ that write_obj
+    wrote, or of a plain `v` / `f` file: triangle faces only, `f a b c`, `f a/ta ...` or `f a/ta/na ...` with positive or negative
+    indices; map_Kd of the first material library names the texture."""
+    v, vt, f, ft, texture = [], [], [], [], None
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if tok[0] == "v":
+                v.append([float(x) for x in tok[1:4]])
+            elif tok[0] == "vt":
+                vt.append([float(x) for x in tok[1:3]])
+            elif tok[0] == "f":
+                if len(tok) != 4:
+                    raise ValueError("%s: only triangle faces are supported" % path)
+                parts = [x.split("/") for x in tok[1:]]
+                f.append([int(x[0]) for x in parts])
+                if all(len(x) > 1 and x[1] for x in parts):
+                    ft.append([int(x[1]) for x in parts])
+            elif tok[0] == "mtllib" and texture is None:
+                mtl = os.path.join(os.path.dirname(path), line.split(None, 1)[1].strip())
+                if os.path.exists(mtl):
+                    for ml in open(mtl):
+                        if ml.split() and ml.split()[0] == "map_Kd":
+                            texture = ml.split(None, 1)[1].strip()
+                            break
+    verts = np.asarray(v, np.float32).reshape(-1, 3)
+    tris = np.asarray(f, np.int64).reshape(-1, 3)
+    tris = np.where(tris < 0, tris + len(verts), tris - 1).astype(np.int32)
+    uv = None
+    if ft:
+        if len(ft) != len(f):
+            raise ValueError("%s: some faces carry texture coordinates and some do not" % path)
+        idx = np.asarray(ft, np.int64)
+        idx = np.where(idx < 0, idx + len(vt), idx - 1)
+        uv = np.asarray(vt, np.float32).reshape(-1, 2)[idx]
+    return verts, tris, uv, texture
 
 
 def read_cameras_json(path, device="cuda"):

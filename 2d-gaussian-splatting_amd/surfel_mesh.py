@@ -483,6 +483,10 @@ def build_parser():
                     "the post-processed mesh clustered on a grid of this many voxels per cell (SIMPLIFY.md)")
     ap.add_argument("--simplify_faces", default=None, type=int, help="Mesh: the same file, with the grid chosen so that at most this many triangles "
                     "remain")
+    ap.add_argument("--texture", action="store_true", help="Mesh: also write fuse_post_textured.{obj,mtl,png} (fuse_unbounded_post_textured.*): the "
+                    "post-processed mesh — the simplified one when a --simplify_* flag is given — with the fused views baked into a texture "
+                    "atlas (TEXTURE.md)")
+    ap.add_argument("--atlas_size", default=4096, type=int, help="Mesh: the side of --texture's atlas in texels")
     return ap
 
 
@@ -571,6 +575,13 @@ def main(argv=None):
         surfel_io.write_triangle_mesh(simple_path, simple)
         print("mesh simplified ({} of {} triangles, cell {:g}) saved at {}".format(simple.triangles.shape[0], post.triangles.shape[0], stats["cell"],
                                                                                   simple_path))
+    if args.texture:      # from the views reconstruction() holds: no second render
+        import surfel_texture
+        base = simple if (args.simplify_cell is not None or args.simplify_faces is not None) else post
+        tm = surfel_texture.texture_mesh(base, cams, ext.rgbmaps, atlas_size=args.atlas_size)
+        paths = surfel_texture.save_textured_mesh(os.path.join(out, name.replace(".ply", "_post_textured")), tm, png=args.png)
+        print("mesh textured ({} triangles, atlas {} x {}, {} of {} owned texels seen) saved at {}".format(
+            base.triangles.shape[0], tm.atlas.shape[1], tm.atlas.shape[0], tm.seen, tm.owned, paths[0]))
     if args.render_path and args.render_mesh:
         render_mesh_path(post)
     return 0

@@ -27,6 +27,7 @@ _n.load()
 DEFAULT_BUDGET = _c.DEFAULT_BUDGET
 ZNEAR, ZFAR = 0.01, 1000.0
 MODES = ("shaded", "normal", "color", "depth")
+TEXTURED = "textured"                                      # render_mesh's mode that takes a surfel_texture.TexturedMesh (TEXTURE.md)
 _KERNEL_MODE = {"shaded": 0, "normal": 1, "color": 2}      # SURFEL_MESHVIEW_SHADED, _NORMAL, _COLOR
 MAX_SSAA = 4                                               # SURFEL_MESHVIEW_MAX_SSAA
 NORMAL_SCALE = 1 << 20                                     # SURFEL_MESHVIEW_NORMAL_SCALE
@@ -210,16 +211,16 @@ def mesh_depth_limits(depth):
 
 @torch.no_grad()
 def render_mesh(mesh, cameras, mode="shaded", smooth=True, albedo="color", ssaa=2, background=(1.0, 1.0, 1.0), budget_bytes=DEFAULT_BUDGET,
-                znear=ZNEAR, zfar=ZFAR, normals=None, depth_range=None):
+                znear=ZNEAR, zfar=ZFAR, normals=None, depth_range=None, texture=None):
     """uint8 [n, H, W, 3] frames of the mesh (on the device).  cameras: a list of the project's cameras or MiniCams of one size, or
     (w2c [n, 3 | 4, 4], intrinsics, H, W).  mode: "shaded" (albedo x headlight), "normal" (world-space normal x 0.5 + 0.5, the convention
     of vis/normal_%05d.png), "color" (vertex colours) or "depth" (turbo of log depth, surfel_path.colorize_depth).  smooth: vertex
     normals (computed here unless `normals` passes them in), else face normals.  albedo: "color" or "grey" (0.8; also for a mesh without
     colours).  ssaa 1 .. 4: samples per pixel edge.  The views go through the device in batches whose keys and frames fit budget_bytes
     (at least one view); views of one size share their batches.  "depth" samples once per pixel; depth_range = (lo, hi) of log depth,
-    default: the 3rd and 97th percentile of the first view's covered pixels (waits on the host)."""
-    if mode not in MODES:
-        raise ValueError("surfel_meshview: mode must be one of %s, got %r" % (", ".join(MODES), mode))
+    default: the 3rd and 97th percentile of the first view's covered pixels (waits on the host).  mode "textured": "color" with the
+    colours of texture, a surfel_texture.TexturedMesh of this mesh (its atlas and texture coordinates)."""
+    _check_mode(mode, texture)
     s = 1 if mode == "depth" else int(ssaa)
     if not 1 <= s <= MAX_SSAA:
         raise ValueError("surfel_meshview: ssaa must be 1 .. %d, got %r" % (MAX_SSAA, ssaa))
@@ -236,10 +237,18 @@ def render_mesh(mesh, cameras, mode="shaded", smooth=True, albedo="color", ssaa=
         return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=dev)
     H, W, _, w2c, k = groups[0]
     w, ks = _c._cameras(w2c, scaled_intrinsics(k, s), dev)
-    return _render_uploaded(mesh, w, ks, H, W, s, mode, normals, albedo, background, znear, zfar, budget_bytes, depth_range)[0]
+    return _render_uploaded(mesh, w, ks, H, W, s, mode, normals, albedo, background, znear, zfar, budget_bytes, depth_range, texture)[0]
 
 
-def _render_uploaded(mesh, w, ks, H, W, s, mode, normals, albedo, background, znear, zfar, budget_bytes, depth_range):
+def _check_mode(mode, texture):
+    if mode == TEXTURED:
+        if texture is None:
+            raise ValueError("surfel_meshview: mode 'textured' needs texture=, a surfel_texture.TexturedMesh")
+    elif mode not in MODES:
+        raise ValueError("surfel_meshview: mode must be one of %s, got %r" % (", ".join(MODES + (TEXTURED,)), mode))
+
+
+def _render_uploaded(mesh, w, ks, H, W, s, mode, normals, albedo, background, znear, zfar, budget_bytes, depth_range, texture=None):
     """render_mesh behind the cameras' upload: w [n, 12] and ks [n, 4] (the sample grid's intrinsics) on the device.  Returns the frames
     and the depth range that was used.  Nothing here waits on the host, except for the depth limits when a "depth" call brings none."""
     n = w.shape[0]
@@ -254,6 +263,9 @@ def _render_uploaded(mesh, w, ks, H, W, s, mode, normals, albedo, background, zn
                 lo_hi = mesh_depth_limits(depth[0])
             for i in range(depth.shape[0]):
                 _sp.colorize_depth(depth[i], lo_hi[0], lo_hi[1], out=out[b + i])
+        elif mode == TEXTURED:
+            import surfel_texture
+            surfel_texture.shade(texture, key, w[b:b + step], ks[b:b + step], H, W, s, background, out=out[b:b + step])
         else:
             shade(mesh, key, w[b:b + step], ks[b:b + step], H, W, s, mode, normals, albedo, background, out=out[b:b + step])
         del key
@@ -277,16 +289,15 @@ def render_mesh_cameras(mesh, cameras, **kw):
 @torch.no_grad()
 def render_mesh_path(mesh, cameras, out_dir, n_frames=240, modes=("shaded", "normal"), video=False, video_only=False, png="pillow", smooth=True,
                      albedo="color", ssaa=2, background=(1.0, 1.0, 1.0), workers=4, video_quality=95, fps=60, znear=ZNEAR, zfar=ZFAR, path=True,
-                     timings=None):
+                     timings=None, texture=None):
     """The mesh along surfel_path.generate_path's trajectory through `cameras` (the one render_path flies): out_dir/mesh/{mode}_%05d.png
     through a FrameWriter and, with video, out_dir/render_traj_mesh_{mode}.avi through a VideoWriter (video_only: the videos and no
     frame files).  path=False: one frame per camera of `cameras` instead (they may differ in size; no video then unless they share one).
     The loop does not wait on the host per frame: the one wait is frame 0's depth limits when "depth" is among the modes.  Returns the
-    cameras that were rendered."""
+    cameras that were rendered.  texture: the surfel_texture.TexturedMesh of the mode "textured"."""
     import time
     for m in modes:
-        if m not in MODES:
-            raise ValueError("surfel_meshview: mode must be one of %s, got %r" % (", ".join(MODES), m))
+        _check_mode(m, texture)
     traj = _sp.generate_path(cameras, n_frames=n_frames) if path else list(cameras)
     video = video or video_only
     os.makedirs(out_dir, exist_ok=True)
@@ -321,7 +332,7 @@ def render_mesh_path(mesh, cameras, out_dir, n_frames=240, modes=("shaded", "nor
                 g = 1 if m == "depth" else int(ssaa)
                 w, ks = grids[g]
                 frames, used = _render_uploaded(mesh, w[j:j + 1], ks[j:j + 1], H, W, g, m, normals if m in ("shaded", "normal") else None, albedo,
-                                                background, znear, zfar, DEFAULT_BUDGET, lo_hi)
+                                                background, znear, zfar, DEFAULT_BUDGET, lo_hi, texture)
                 frame = frames[0]
                 if m == "depth":
                     lo_hi = used      # (frame 0's limits serve every frame)
@@ -370,7 +381,8 @@ def build_parser():
                     "one frame per camera, to compare with train/ours_N/renders (train)")
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--n_frames", type=int, default=240)
-    ap.add_argument("--mesh_modes", nargs="+", default=["shaded", "normal"], choices=list(MODES))
+    ap.add_argument("--mesh_modes", nargs="+", default=["shaded", "normal"], choices=list(MODES) + [TEXTURED],
+                    help="textured: --ply-path names an .obj that surfel_texture.py or surfel_mesh.py --texture wrote")
     ap.add_argument("--mesh_ssaa", type=int, default=2, choices=[1, 2, 3, 4])
     ap.add_argument("--flat", action="store_true", help="face normals instead of vertex normals")
     ap.add_argument("--albedo", type=str, default="color", choices=["color", "grey"])
@@ -398,13 +410,21 @@ def main(argv=None):
     if (args.traj_path is None) == (args.model_path is None):
         raise SystemExit("give --traj-path or -m MODEL_DIR")
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
-    stem = args.ply_path[:-4] if args.ply_path.endswith(".ply") else args.ply_path
+    texture = None
+    if args.ply_path.endswith(".obj"):
+        import surfel_texture
+        texture = surfel_texture.load_textured_mesh(args.ply_path, dev)
+        mesh = texture.mesh
+    else:
+        v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
+        mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+    if TEXTURED in args.mesh_modes and texture is None:
+        raise SystemExit("--mesh_modes textured needs an .obj with a texture")
+    stem = args.ply_path[:-4] if args.ply_path.endswith((".ply", ".obj")) else args.ply_path
     out = args.out or stem + "_view"
     common = dict(modes=tuple(args.mesh_modes), video=args.video, video_only=args.video_only, png=args.png, smooth=not args.flat, albedo=args.albedo,
                   ssaa=args.mesh_ssaa, background=(0.0, 0.0, 0.0) if args.black_background else (1.0, 1.0, 1.0), video_quality=args.video_quality,
-                  fps=args.fps, znear=args.near, zfar=args.far)
+                  fps=args.fps, znear=args.near, zfar=args.far, texture=texture)
     if args.model_path is not None:
         cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=dev)
         traj = render_mesh_path(mesh, cams, out, n_frames=args.n_frames, path=args.views == "path", **common)

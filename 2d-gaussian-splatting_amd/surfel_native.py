@@ -202,6 +202,13 @@ SIGNATURES = {
         "surfel_simplify_count": (_i64, _a, _u, _i64, _i64, _d, _d, _fp, _fp, _f, _i64p, _s),
         "surfel_simplify_mesh": (_i, _a, _u, _i64, _i64, _d, _d, _d, _fp, _fp, _f, _f64, _d, _d, _d, _d, _d, _i64p, _fp, _s),
     },
+    "surfel_texture.h": {
+        "surfel_texture_classify": (_i, _a, _u, _i64, _i64, _d, _d, _f, _d, _i64p, _s),      # counts, table: HOST pointers
+        "surfel_texture_layout": (_i64, _a, _u, _i64, _i64, _d, _d, _d, _i64p, _i, _ip, _d, _d, _s),
+        "surfel_texture_bake": (_i, _i64, _i64, _d, _d, _ip, _d, _i, _i, _i, _d, _d, _i, _i, _i, _d, _d, _f, _f, _i, _i, _d, _s),
+        "surfel_texture_resolve": (_i, _i64, _i64, _d, _d, _d, _ip, _d, _i, _i, _d, _i, _f, _f, _f, _d, _d, _s),
+        "surfel_texture_shade": (_i, _i64, _i64, _d, _d, _d, _d, _i, _i, _i, _d, _d, _i, _i, _i, _i, _d, _f, _f, _f, _d, _s),
+    },
     "surfel_jpeg.h": {
         "surfel_jpeg_capacity": (_i64, _i, _i),
         "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
@@ -240,6 +247,7 @@ VIEW_EXPORTS = list(SIGNATURES["surfel_view.h"])
 CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 MESHVIEW_EXPORTS = list(SIGNATURES["surfel_meshview.h"])
 SIMPLIFY_EXPORTS = list(SIGNATURES["surfel_simplify.h"])
+TEXTURE_EXPORTS = list(SIGNATURES["surfel_texture.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])

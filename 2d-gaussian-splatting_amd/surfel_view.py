@@ -7,7 +7,7 @@ include/surfel_vis.h) that turn the render package into the interleaved bytes of
 never leaving the device — one non-blocking copy into a pinned buffer that is reused from frame to frame, one event wait, and the
 socket.  The protocol is host code.
 
-    python surfel_view.py -m MODEL [-s CAPTURE] [--iteration N] [--ip 127.0.0.1] [--port 6009] [--mesh MESH.ply]
+    python surfel_view.py -m MODEL [-s CAPTURE] [--iteration N] [--ip 127.0.0.1] [--port 6009] [--mesh MESH.ply | MESH.obj]
 """
 import json
 import os
@@ -24,6 +24,7 @@ _n.load()
 
 RENDER_ITEMS = ["RGB", "Alpha", "Normal", "Depth", "Edge", "Curvature"]      # arguments/__init__.py:57, the order the viewer's menu indexes
 MESH_ITEMS = {"Mesh": "shaded", "Mesh Normal": "normal"}      # appended to the menu of a Viewer that was given a mesh (MESHVIEW.md)
+TEXTURE_ITEMS = {"Mesh Textured": "textured"}                 # and behind them for a mesh that came with a texture (TEXTURE.md)
 DEFAULT_TIMEOUT = 5.0      # seconds a connected viewer may stay silent (or not read) before it is dropped
 
 
@@ -168,11 +169,13 @@ class Viewer:
     """The listener (None for a Viewer attached to a socket that is connected already) and the one connection.  serve() is what a
     training loop calls after every step, and what the stand-alone viewer calls forever."""
 
-    def __init__(self, host="127.0.0.1", port=6009, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, listener=True, mesh=None):
+    def __init__(self, host="127.0.0.1", port=6009, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, listener=True, mesh=None, texture=None):
         self.timeout, self.device, self.items = timeout, device, list(items)
         self.mesh, self._mesh_normals = mesh, None      # a surfel_mesh.TriangleMesh on the device: two more items, served by surfel_meshview
+        self.texture = texture                          # a surfel_texture.TexturedMesh of that mesh: one more item
+        self._mesh_items = dict(MESH_ITEMS, **TEXTURE_ITEMS) if texture is not None else dict(MESH_ITEMS)
         if mesh is not None:
-            self.items += list(MESH_ITEMS)
+            self.items += list(self._mesh_items)
         self.listener = open_listener(host, port) if listener else None
         self.conn = None
         self.frames = 0
@@ -180,9 +183,9 @@ class Viewer:
         self._event = None
 
     @classmethod
-    def attached(cls, sock, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, mesh=None):
+    def attached(cls, sock, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, mesh=None, texture=None):
         """A Viewer on a connected socket object (one end of a socketpair, an accepted connection): no listener, nothing is bound."""
-        v = cls(timeout=timeout, device=device, items=items, listener=False, mesh=mesh)
+        v = cls(timeout=timeout, device=device, items=items, listener=False, mesh=mesh, texture=texture)
         v._adopt(sock)
         return v
 
@@ -234,13 +237,15 @@ class Viewer:
         if self.mesh is None:
             return None
         if isinstance(render_mode, str):
-            return next((m for name, m in MESH_ITEMS.items() if name.lower() == render_mode.lower()), None)
-        first = len(self.items) - len(MESH_ITEMS)      # (the mesh items are the last ones of the menu)
-        return MESH_ITEMS[self.items[render_mode]] if first <= render_mode < len(self.items) else None
+            return next((m for name, m in self._mesh_items.items() if name.lower() == render_mode.lower()), None)
+        first = len(self.items) - len(self._mesh_items)      # (the mesh items are the last ones of the menu)
+        return self._mesh_items[self.items[render_mode]] if first <= render_mode < len(self.items) else None
 
     def _mesh_image(self, cam, mode):
         """uint8 [H, W, 3] on the device: the mesh for the viewer's camera, one sample per pixel, on white (surfel_meshview.render_mesh)"""
         import surfel_meshview
+        if mode == "textured":
+            return surfel_meshview.render_mesh(self.mesh, [cam], mode=mode, ssaa=1, texture=self.texture)[0]
         if self._mesh_normals is None:
             self._mesh_normals = surfel_meshview.vertex_normals(self.mesh)
         return surfel_meshview.render_mesh(self.mesh, [cam], mode=mode, ssaa=1, normals=self._mesh_normals)[0]
@@ -284,7 +289,8 @@ def build_parser():
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--ip", type=str, default="127.0.0.1")
     ap.add_argument("--port", type=int, default=6009)
-    ap.add_argument("--mesh", type=str, default=None, help="a mesh (.ply) to show as two more menu items, Mesh and Mesh Normal (MESHVIEW.md)")
+    ap.add_argument("--mesh", type=str, default=None, help="a mesh (.ply) to show as two more menu items, Mesh and Mesh Normal (MESHVIEW.md); "
+                    "an .obj with a texture (TEXTURE.md) adds Mesh Textured")
     return ap
 
 
@@ -306,12 +312,16 @@ def main(argv=None):
     pipe = argparse.Namespace(depth_ratio=args.depth_ratio, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
     background = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
     print("View: " + args.model_path)
-    mesh = None
-    if args.mesh is not None:
+    mesh = texture = None
+    if args.mesh is not None and args.mesh.endswith(".obj"):
+        import surfel_texture
+        texture = surfel_texture.load_textured_mesh(args.mesh, dev)
+        mesh = texture.mesh
+    elif args.mesh is not None:
         import surfel_io
         from surfel_mesh import TriangleMesh
         mesh = TriangleMesh(*(torch.from_numpy(a).to(dev) for a in surfel_io.read_triangle_mesh(args.mesh)))
-    viewer = Viewer(args.ip, args.port, mesh=mesh)
+    viewer = Viewer(args.ip, args.port, mesh=mesh, texture=texture)
     metrics = {"#": int(gaussians.get_opacity.shape[0])}
     try:
         while True:      # (train = 0 keeps serve() inside; a dropped viewer brings it back here to wait for the next one)
