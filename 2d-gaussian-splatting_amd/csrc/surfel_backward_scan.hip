@@ -74,6 +74,8 @@ __device__ __forceinline__ int select_bit128(unsigned long long w0, unsigned lon
 #ifndef SCAN_FLUSH_GROUP
 #define SCAN_FLUSH_GROUP 4      // 4: 167 / 168 VGPRs, no spills; 2: the same, garden step 3.207 against 3.201 ms; 8 and 16 spill 18 - 102 dwords at the 168-register limit
 #endif
+// (Skipping the group of a wave whose lists ended before the round — a scalar branch per group — was measured as no gain on garden:
+// profiles/r08_negative_results.md section 1.)
 template <int NQ, int FG, bool GUARD>
 __device__ __forceinline__ void flush_round(const float4* slots, const float4* zs, const uint4 frk, const int c, float4 (&f)[NQ]) {
     const uint32_t rkw[4] = {frk.x, frk.y, frk.z, frk.w};
@@ -148,7 +150,11 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
     __shared__ unsigned long long s_bal[16][SB / 64];         // per sub-tile: the staged instances on its list
     __shared__ uint8_t s_list[16][SB];                        // per sub-tile: its list (staged indices, back to front)
     __shared__ uint4 s_rank[SB];                              // per staged instance: its rank on each of the 16 lists (0xff: not on it)
-    __shared__ uint32_t s_cmm[SB];                            // per staged instance: first | last << 8 round it takes part in
+    // per staged instance: first | last << 8 round it takes part in, by its lists of sub-tiles 0-7 and of 8-15.  16-bit: the kernel's
+    // 53 384 B stay as they are — with 32-bit words here (53 896 B, three times that still below a CU's 160 KB) the third workgroup
+    // is gone: garden blend_bwd 1.14 -> 1.33 ms (profiles/r08_scan_batch_whatif.jsonl, arm `big`; it fits LDS being granted in pieces
+    // of 1 280 B, 42 of them = 53 760 B the most for three workgroups, profiles/r08_scan_batch_isa.md section 3).
+    __shared__ uint16_t s_cmm[2][SB];
     __shared__ int s_rowlast[16];
     __shared__ int s_max;
     const int tid = threadIdx.x;
@@ -305,27 +311,35 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
                     if (fh == 0) { pa = src[0]; pb = src[1]; pc = src[3]; pd = src[4]; } else { pa = src[2]; pb = src[5]; pc = src[6]; }
                 }
             }
-            if (ft >= keep) ovr = 0;
         }
         const unsigned long long km0 = keep >= 64 ? ~0ull : ((1ull << keep) - 1ull);
         const unsigned long long km1 = keep >= 128 ? ~0ull : (keep > 64 ? ((1ull << (keep - 64)) - 1ull) : 0ull);
-        if (fh == 1) {                        // (the threads that hold the footprints)
-            // rank of this instance on every list it is on = instances ahead of it (staged order = back to front) on that list
-            uint32_t rk[4] = {~0u, ~0u, ~0u, ~0u};
-            uint32_t cmin = 255u, cmax = 0u;
-            const unsigned long long lt = (1ull << (ft & 63)) - 1ull;
+        {
+            // rank of this instance on every list it is on = instances ahead of it (staged order = back to front) on that list.
+            // All four waves: thread (ft, fh) takes the lists of sub-tiles 8 fh .. 8 fh + 7 (with the sixteen lists on the two waves
+            // that hold the footprints, the other two waited at the barrier for twice as long: a second pass over the old block cost
+            // garden 0.083 of 1.14 ms, profiles/r08_scan_batch_whatif.jsonl).  Whether the instance is on list s is bit ft of the
+            // sub-tile's ballot.  The ballots need no truncation to `keep` here: an instance that is walked (ft < keep) has only walked
+            // instances ahead of it, and one that is not walked is on no list.
+            uint32_t rk[2] = {~0u, ~0u};
+            uint32_t rmin = 16u * 255u, rmax = 0u;      // lowest and highest rank: their rounds are the instance's first and last
+            const bool lo64 = ft < 64;
+            const int sh = 8 * __builtin_amdgcn_readfirstlane(fh);
+            const unsigned long long bit = ft < keep ? 1ull << (ft & 63) : 0ull, lt = (1ull << (ft & 63)) - 1ull;
 #pragma unroll
-            for (int s = 0; s < 16; s++) {
-                const unsigned long long m0 = s_bal[s][0] & km0, m1 = s_bal[s][1] & km1;
-                const uint32_t r = ft < 64 ? (uint32_t)__popcll(m0 & lt) : (uint32_t)(__popcll(m0) + __popcll(m1 & lt));
-                if ((ovr >> s) & 1u) {
+            for (int j = 0; j < 8; j++) {
+                const int s = sh + j;
+                const unsigned long long m0 = s_bal[s][0], m1 = s_bal[s][1];
+                const unsigned long long mw = lo64 ? m0 : m1;
+                const uint32_t r = (lo64 ? 0u : (uint32_t)__popcll(m0)) + (uint32_t)__popcll(mw & lt);
+                if (mw & bit) {
                     s_list[s][r] = (uint8_t)ft;
-                    rk[s >> 2] = (rk[s >> 2] & ~(0xffu << (8 * (s & 3)))) | (r << (8 * (s & 3)));
-                    cmin = min(cmin, r >> 4); cmax = max(cmax, r >> 4);
+                    rk[j >> 2] = (rk[j >> 2] & ~(0xffu << (8 * (j & 3)))) | (r << (8 * (j & 3)));
+                    rmin = min(rmin, r); rmax = max(rmax, r);
                 }
             }
-            s_rank[ft] = make_uint4(rk[0], rk[1], rk[2], rk[3]);
-            s_cmm[ft] = cmin | (cmax << 8);      // an instance on no list: 255 | 0 -> takes part in no round
+            reinterpret_cast<uint2*>(s_rank)[2 * ft + fh] = make_uint2(rk[0], rk[1]);
+            s_cmm[fh][ft] = (uint16_t)((rmin >> 4) | ((rmax >> 4) << 8));      // on none of these eight lists: 255 | 0 -> by this half, part of no round
         }
         // list length of this row's sub-tile, and the number of rounds = chunks of the longest list (the same in every thread)
         const int n_row = __popcll(s_bal[srow][0] & km0) + __popcll(s_bal[srow][1] & km1);
@@ -333,8 +347,13 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
         nmax = max(nmax, __shfl_xor(nmax, 1)); nmax = max(nmax, __shfl_xor(nmax, 2)); nmax = max(nmax, __shfl_xor(nmax, 4)); nmax = max(nmax, __shfl_xor(nmax, 8));
         const int nrounds = (nmax + CH - 1) / CH;
         __syncthreads();
-        const uint32_t fcm = s_cmm[ft];
-        const int fcmin = (int)(fcm & 255u), fcmax = (int)(fcm >> 8);
+        // first and last round of this thread's instance: the earlier first and the later last of its two halves of the lists
+        auto rounds_of = [&](int& first, int& last) {
+            const uint32_t l = s_cmm[0][ft], h = s_cmm[1][ft];
+            first = (int)min(l & 255u, h & 255u); last = (int)max(l >> 8, h >> 8);
+        };
+        int fcmin, fcmax;
+        rounds_of(fcmin, fcmax);
 
         for (int c = 0; c < nrounds; c++) {
             const int idx = c * CH + i16;
@@ -467,6 +486,7 @@ __global__ void __launch_bounds__(BLOCK, SCAN_MIN_WG) blend_bwd_scan_kernel(Blen
             __syncthreads();
             // ---- flush round c: the slot of (sub-tile s, lane r & 15) belongs to the instance of rank r = 16 c + lane on list s.
             // Fixed order: rounds ascending, sub-tiles ascending inside a round.
+            if (STATS) rounds_of(fcmin, fcmax);      // (the instrumented instantiations read them again: kept across the walk they are spilled)
             if (ft < mb && c >= fcmin && c <= fcmax) {
                 // (the ranks are re-read every round: kept in registers, the compiler hoists sixteen slot addresses per thread out
                 // of the round loop and spills them across the walk)
