@@ -487,6 +487,11 @@ def build_parser():
                     "post-processed mesh — the simplified one when a --simplify_* flag is given — with the fused views baked into a texture "
                     "atlas (TEXTURE.md)")
     ap.add_argument("--atlas_size", default=4096, type=int, help="Mesh: the side of --texture's atlas in texels")
+    ap.add_argument("--smooth_iterations", default=None, type=int, help="Mesh: also write fuse_post_smoothed.ply (fuse_unbounded_post_smoothed.ply), "
+                    "the post-processed mesh after this many filter iterations (SMOOTH.md); --simplify_* and --texture then continue from it")
+    ap.add_argument("--smooth_method", default="taubin", choices=["taubin", "laplacian"], help="Mesh: the filter of --smooth_iterations")
+    ap.add_argument("--smooth_boundary", default="free", choices=["free", "fixed", "curve"], help="Mesh: what --smooth_iterations does at the "
+                    "mesh's border: every neighbour counts, boundary vertices stay, or they average along the border only")
     return ap
 
 
@@ -508,6 +513,8 @@ def main(argv=None):
         raise SystemExit("give --simplify_cell or --simplify_faces, not both")
     if args.simplify_cell is not None and not args.simplify_cell > 0:
         raise SystemExit("--simplify_cell must be positive")
+    if args.smooth_iterations is not None and args.smooth_iterations < 0:
+        raise SystemExit("--smooth_iterations must not be negative")
     import surfel_io
     import surfel_model
     from surfel_render import render
@@ -567,6 +574,13 @@ def main(argv=None):
     post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
     surfel_io.write_triangle_mesh(os.path.join(out, name.replace(".ply", "_post.ply")), post)
     print("mesh post processed saved at {}".format(os.path.join(out, name.replace(".ply", "_post.ply"))))
+    if args.smooth_iterations is not None:      # the steps below continue from the smoothed mesh
+        import surfel_smooth
+        post, stats = surfel_smooth.smooth_mesh(post, iterations=args.smooth_iterations, method=args.smooth_method, boundary=args.smooth_boundary)
+        smooth_path = os.path.join(out, name.replace(".ply", "_post_smoothed.ply"))
+        surfel_io.write_triangle_mesh(smooth_path, post)
+        print("mesh smoothed ({}, {} steps, {} border and {} non-manifold edges) saved at {}".format(args.smooth_method, stats["steps"],
+                                                                                                 stats["border_edges"], stats["nonmanifold_edges"], smooth_path))
     if args.simplify_cell is not None or args.simplify_faces is not None:
         import surfel_simplify
         cell = None if args.simplify_cell is None else args.simplify_cell * voxel_size

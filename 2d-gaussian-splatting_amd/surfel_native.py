@@ -209,6 +209,10 @@ SIGNATURES = {
         "surfel_texture_resolve": (_i, _i64, _i64, _d, _d, _d, _ip, _d, _i, _i, _d, _i, _f, _f, _f, _d, _d, _s),
         "surfel_texture_shade": (_i, _i64, _i64, _d, _d, _d, _d, _i, _i, _i, _d, _d, _i, _i, _i, _i, _d, _f, _f, _f, _d, _s),
     },
+    "surfel_smooth.h": {
+        "surfel_smooth_adjacency": (_i64, _a, _u, _i64, _i64, _d, _d, _d, _d, _d, _d, _i64p, _s),      # counts, factors: HOST pointers
+        "surfel_smooth_steps": (_i, _i64, _d, _d, _d, _d, _i, _i, _f64p, _d, _d, _d, _s),
+    },
     "surfel_jpeg.h": {
         "surfel_jpeg_capacity": (_i64, _i, _i),
         "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
@@ -248,6 +252,7 @@ CULL_EXPORTS = list(SIGNATURES["surfel_cull.h"])
 MESHVIEW_EXPORTS = list(SIGNATURES["surfel_meshview.h"])
 SIMPLIFY_EXPORTS = list(SIGNATURES["surfel_simplify.h"])
 TEXTURE_EXPORTS = list(SIGNATURES["surfel_texture.h"])
+SMOOTH_EXPORTS = list(SIGNATURES["surfel_smooth.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])

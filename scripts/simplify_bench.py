@@ -22,17 +22,6 @@ for p in (REPO, os.path.join(REPO, "2d-gaussian-splatting_amd"), os.path.join(RE
 import torch  # noqa: E402
 
 
-def nonmanifold_edges(tris):
-    """(edges that more than two triangles share, edges of one triangle only) of triangles [F, 3] on the device"""
-    t = tris.to(torch.int64)
-    if t.shape[0] == 0:
-        return 0, 0
-    e = torch.cat([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]])
-    lo, hi = e.min(1).values, e.max(1).values
-    counts = torch.unique(lo * (int(t.max()) + 1) + hi, return_counts=True)[1]
-    return int((counts > 2).sum()), int((counts == 1).sum())
-
-
 def run_case(dev, state, res, mesh, case, repeat=2, **kw):
     import surfel_simplify
     for _ in range(repeat):
@@ -41,7 +30,9 @@ def run_case(dev, state, res, mesh, case, repeat=2, **kw):
         out, stats = surfel_simplify.simplify_mesh(mesh, timings=timings, **kw)
         torch.cuda.synchronize(dev)
         wall = (time.perf_counter() - t0) * 1e3
-    over, border = nonmanifold_edges(out.triangles)
+    import surfel_smooth
+    edges = surfel_smooth.mesh_adjacency(out).stats      # the triangles on every edge, from the vertex adjacency (SMOOTH.md)
+    over, border = edges["nonmanifold_edges"], edges["border_edges"]
     line = {"state": state, "mesh_res": res, "case": case, "V": int(mesh.vertices.shape[0]), "F": int(mesh.triangles.shape[0]),
             "V_out": int(out.vertices.shape[0]), "F_out": int(out.triangles.shape[0]), "cell": float("%.6g" % stats["cell"]), "n": stats["n"],
             "probes": stats["probes"], "clusters": stats["clusters"], "collapsed": stats["collapsed"], "duplicates": stats["duplicates"],
