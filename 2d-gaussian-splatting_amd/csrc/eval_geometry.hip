@@ -360,11 +360,7 @@ inline EGrid egrid_of(const surfel_eval_grid* g) {
     return EGrid{g->origin[0], g->origin[1], g->origin[2], g->cell, g->dims[0], g->dims[1], g->dims[2], g->n,
                  reinterpret_cast<const float4*>(g->sorted), g->order, reinterpret_cast<const uint2*>(g->ranges)};
 }
-inline int key_bits(int64_t ncells) {
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < ncells) bits++;
-    return bits;
-}
+inline int key_bits(int64_t ncells) { return bit_length(ncells - 1); }      // cell indices 0 .. ncells - 1
 constexpr int64_t EVAL_MAX_POINTS = ((int64_t)1 << 31) - 1;
 }  // namespace
 
@@ -386,8 +382,7 @@ int64_t surfel_eval_sample_count(surfel_alloc_fn alloc, void* user, int64_t V, i
                        reinterpret_cast<unsigned long long*>(tail), tail + 2);
     scan_u32(offsets, F, scratch, st);
     uint32_t host[3] = {0, 0, 0};
-    if (hipMemcpyAsync(host, tail, 12, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, "eval_sample_count: copy", hipGetLastError());
+    if (int rc = read_words("eval_sample_count: copy", tail, host, 3, st)) return rc;
     const int rc = launched("eval_sample_count_kernel");
     if (rc < 0) return rc;
     if (host[2]) return api_fail(SURFEL_E_LIMIT, "eval_sample_count: a triangle wants more than SURFEL_EVAL_MAX_N samples along an edge (raise the density)");
@@ -425,17 +420,12 @@ int surfel_eval_grid_build(surfel_alloc_fn alloc, void* user, surfel_eval_grid* 
     if (!g->ranges || !g->sorted || !g->order) return api_fail(SURFEL_E_ALLOC, "eval_grid_build: allocator returned NULL");
     if (hipMemsetAsync(g->ranges, 0, (size_t)nc * 8, st) != hipSuccess) return api_fail(SURFEL_E_HIP, "eval_grid_build: memset", hipGetLastError());
     if (n == 0) return 0;
-    uint32_t* ka = take<uint32_t>(alloc, user, n);
-    uint32_t* va = take<uint32_t>(alloc, user, n);
-    uint32_t* kb = take<uint32_t>(alloc, user, n);
-    uint32_t* vb = take<uint32_t>(alloc, user, n);
-    void* scratch = alloc(user, sort_bytes);
-    if (!ka || !va || !kb || !vb || !scratch) return api_fail(SURFEL_E_ALLOC, "eval_grid_build: allocator returned NULL");
+    SortPairs s(alloc, user, n);
+    if (!s.ok()) return api_fail(SURFEL_E_ALLOC, "eval_grid_build: allocator returned NULL");
     const EGrid eg = egrid_of(g);
-    hipLaunchKernelGGL(eval_keys_kernel, dim3(grid(n)), dim3(ET), 0, st, eg, n, points, ka, va);
-    const int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, key_bits(nc), scratch, st);
-    if (r < 0) return api_fail(SURFEL_E_LIMIT, "eval_grid_build: sort");
-    hipLaunchKernelGGL(eval_gather_kernel, dim3(grid(n)), dim3(ET), 0, st, eg, n, points, rank, r ? kb : ka, r ? vb : va,
+    hipLaunchKernelGGL(eval_keys_kernel, dim3(grid(n)), dim3(ET), 0, st, eg, n, points, s.ka, s.va);
+    if (s.sort(key_bits(nc), st) < 0) return api_fail(SURFEL_E_LIMIT, "eval_grid_build: sort");
+    hipLaunchKernelGGL(eval_gather_kernel, dim3(grid(n)), dim3(ET), 0, st, eg, n, points, rank, s.ka, s.va,
                        reinterpret_cast<float4*>(g->sorted), g->order, g->ranges);
     return launched("eval_gather_kernel");
 }
@@ -461,8 +451,7 @@ int surfel_eval_thin(surfel_alloc_fn alloc, void* user, const surfel_eval_grid* 
         if (hipMemsetAsync(decided, 0, BATCH * 4, st) != hipSuccess) return api_fail(SURFEL_E_HIP, "eval_thin: memset", hipGetLastError());
         for (int b = 0; b < BATCH; b++) hipLaunchKernelGGL(eval_thin_round_kernel, dim3(grid(n)), dim3(ET), 0, st, eg, dd, state, decided + b);
         uint32_t host[BATCH];
-        if (hipMemcpyAsync(host, decided, BATCH * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return api_fail(SURFEL_E_HIP, "eval_thin: copy", hipGetLastError());
+        if (int rc = read_words("eval_thin: copy", decided, host, BATCH, st)) return rc;
         const int rc = launched("eval_thin_round_kernel");
         if (rc < 0) return rc;
         for (int b = 0; b < BATCH && !done; b++) {
@@ -513,17 +502,12 @@ int surfel_eval_nearest(surfel_alloc_fn alloc, void* user, const surfel_eval_gri
         hipLaunchKernelGGL(eval_fill_none_kernel, dim3(grid(nq)), dim3(ET), 0, st, nq, dist, index);
         return launched("eval_fill_none_kernel");
     }
-    uint32_t* ka = take<uint32_t>(alloc, user, nq);
-    uint32_t* va = take<uint32_t>(alloc, user, nq);
-    uint32_t* kb = take<uint32_t>(alloc, user, nq);
-    uint32_t* vb = take<uint32_t>(alloc, user, nq);
-    void* scratch = alloc(user, radix_sort_scratch_bytes((size_t)nq));
-    if (!ka || !va || !kb || !vb || !scratch) return api_fail(SURFEL_E_ALLOC, "eval_nearest: allocator returned NULL");
+    SortPairs s(alloc, user, nq);
+    if (!s.ok()) return api_fail(SURFEL_E_ALLOC, "eval_nearest: allocator returned NULL");
     const EGrid eg = egrid_of(g);
-    hipLaunchKernelGGL(eval_query_keys_kernel, dim3(grid(nq)), dim3(ET), 0, st, eg, nq, queries, ka, va);
-    const int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)nq, 0, key_bits(cells_of(g)), scratch, st);
-    if (r < 0) return api_fail(SURFEL_E_LIMIT, "eval_nearest: sort");
-    hipLaunchKernelGGL(eval_nearest_kernel, dim3(grid(nq)), dim3(ET), 0, st, eg, nq, queries, r ? vb : va, max_dist, dist, index);
+    hipLaunchKernelGGL(eval_query_keys_kernel, dim3(grid(nq)), dim3(ET), 0, st, eg, nq, queries, s.ka, s.va);
+    if (s.sort(key_bits(cells_of(g)), st) < 0) return api_fail(SURFEL_E_LIMIT, "eval_nearest: sort");
+    hipLaunchKernelGGL(eval_nearest_kernel, dim3(grid(nq)), dim3(ET), 0, st, eg, nq, queries, s.va, max_dist, dist, index);
     return launched("eval_nearest_kernel");
 }
 

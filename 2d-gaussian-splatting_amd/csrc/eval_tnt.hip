@@ -249,42 +249,36 @@ int64_t surfel_tnt_voxel_down_sample(surfel_alloc_fn alloc, void* user, int64_t 
         return api_fail(SURFEL_E_INVALID, "tnt_voxel_down_sample: bad arguments");
     if (n >= ((int64_t)1 << 30) - 1) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: more than 2^30 - 2 points (the sort's limit)");
     const size_t sort_bytes = radix_sort_scratch_bytes((size_t)(n > 0 ? n : 1));
-    const int64_t scan_words = (n + 1) + scan_scratch_u32(n + 1) + 1;      // heads | scan sums | flag
+    const int64_t scan_words = ScanBuf::words(n + 1) + 1;      // heads | scan sums | flag
     if (6 * 4 * n + 4 * scan_words + (int64_t)sort_bytes > budget_bytes)
         return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: the cloud exceeds the byte budget (raise the budget or down-sample the input)");
     if (n == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* lo = take<uint32_t>(alloc, user, n);
     uint32_t* hi = take<uint32_t>(alloc, user, n);
-    uint32_t* ka = take<uint32_t>(alloc, user, n);
-    uint32_t* va = take<uint32_t>(alloc, user, n);
-    uint32_t* kb = take<uint32_t>(alloc, user, n);
-    uint32_t* vb = take<uint32_t>(alloc, user, n);
-    uint32_t* head = take<uint32_t>(alloc, user, scan_words);
-    void* scratch = alloc(user, sort_bytes);
-    if (!lo || !hi || !ka || !va || !kb || !vb || !head || !scratch) return api_fail(SURFEL_E_ALLOC, "tnt_voxel_down_sample: allocator returned NULL");
-    uint32_t* sums = head + (n + 1);
-    uint32_t* flag = sums + scan_scratch_u32(n + 1);
+    SortPairs s(alloc, user, n);
+    const ScanBuf head = take_scan(alloc, user, n + 1, 1);      // (n + 1 elements: the scan leaves the cell count in head[n])
+    if (!lo || !hi || !s.ok() || !head.flags) return api_fail(SURFEL_E_ALLOC, "tnt_voxel_down_sample: allocator returned NULL");
+    uint32_t* flag = head.total + 1;
     if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return api_fail(SURFEL_E_HIP, "tnt_voxel_down_sample: memset", hipGetLastError());
     const TVox v{origin[0], origin[1], origin[2], voxel};
-    hipLaunchKernelGGL(tnt_voxel_keys_kernel, dim3(grid(n)), dim3(TT), 0, st, n, points, v, lo, hi, ka, va, flag);
+    hipLaunchKernelGGL(tnt_voxel_keys_kernel, dim3(grid(n)), dim3(TT), 0, st, n, points, v, lo, hi, s.ka, s.va, flag);
     // the 63-bit key as two stable LSD sorts of its 32-bit halves: low word first, then high word
-    const uint32_t* perm = sort_pairs_two_words(ka, va, kb, vb, n, 32, 3 * AXIS_BITS - 32, scratch, st, [&](const uint32_t* val, uint32_t* key) {
-        hipLaunchKernelGGL(tnt_voxel_hi_kernel, dim3(grid(n)), dim3(TT), 0, st, n, hi, val, key);
-    });
-    if (!perm) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
-    hipLaunchKernelGGL(tnt_voxel_heads_kernel, dim3(grid(n + 1)), dim3(TT), 0, st, n, lo, hi, perm, head);
-    scan_u32(head, n + 1, sums, st);
+    if (s.sort(32, st) < 0) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
+    hipLaunchKernelGGL(tnt_voxel_hi_kernel, dim3(grid(n)), dim3(TT), 0, st, n, hi, s.va, s.ka);
+    if (s.sort(3 * AXIS_BITS - 32, st) < 0) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
+    const uint32_t* perm = s.va;
+    hipLaunchKernelGGL(tnt_voxel_heads_kernel, dim3(grid(n + 1)), dim3(TT), 0, st, n, lo, hi, perm, head.flags);
+    head.scan(st);
     uint32_t host[2] = {0, 0};      // cell count, flag
-    if (hipMemcpyAsync(&host[0], head + n, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&host[1], flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, "tnt_voxel_down_sample: copy", hipGetLastError());
+    if (int rc = read_words("tnt_voxel_down_sample: copy", head.flags + n, &host[0], 1, st, false)) return rc;
+    if (int rc = read_words("tnt_voxel_down_sample: copy", flag, &host[1], 1, st)) return rc;
     int rc = launched("tnt_voxel_heads_kernel");
     if (rc < 0) return rc;
     if (host[1])
         return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: a cell index needs more than SURFEL_TNT_VOXEL_AXIS_BITS bits, or a coordinate is not finite "
                                         "or lies below the origin (raise the voxel size)");
-    hipLaunchKernelGGL(tnt_voxel_mean_kernel, dim3(grid(n)), dim3(TT), 0, st, n, points, lo, hi, perm, head, out, counts, cells);
+    hipLaunchKernelGGL(tnt_voxel_mean_kernel, dim3(grid(n)), dim3(TT), 0, st, n, points, lo, hi, perm, head.flags, out, counts, cells);
     if (hipStreamSynchronize(st) != hipSuccess) return api_fail(SURFEL_E_HIP, "tnt_voxel_down_sample: synchronize", hipGetLastError());
     rc = launched("tnt_voxel_mean_kernel");
     return rc < 0 ? rc : (int64_t)host[0];

@@ -330,7 +330,6 @@ using namespace surfel;
 namespace {
 
 inline unsigned grid(int64_t n) { return blocks_for(n, ST); }
-inline int bit_length(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
 inline float key_float(uint32_t k) {
     const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
     float f;
@@ -356,8 +355,7 @@ int bounds_of(const char* what, int64_t V, const float* verts, surfel_alloc_fn a
     hipLaunchKernelGGL(simp_bounds_reset_kernel, dim3(1), dim3(64), 0, st, keys);
     hipLaunchKernelGGL(simp_bounds_kernel, dim3(grid(V)), dim3(ST), 0, st, V, verts, keys);
     uint32_t host[6];
-    if (hipMemcpyAsync(host, keys, sizeof(host), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, what, hipGetLastError());
+    if (int rc = read_words(what, keys, host, 6, st)) return rc;
     if (int rc = launched("simp_bounds_kernel")) return rc;
     if (host[0] == BOUND_NONE_LO) return 0;
     for (int k = 0; k < 6; k++) bounds[k] = key_float(host[k]);
@@ -376,7 +374,7 @@ struct Simp {
     int64_t nc;                   // occupied cells
     uint64_t* key64; const uint32_t* order; uint32_t* cstart; int32_t* cluster;
     int64_t valid, M, kept;       // triangles that pass rule 1, candidates, survivors
-    int32_t* trip; uint32_t* kpos; uint32_t* ktotal;
+    int32_t* trip; ScanBuf keep;  // the candidates' cell triples, their keep flags (after dedupe_triangles: positions)
     hipEvent_t ev[SURFEL_SIMPLIFY_STAGES + 1]; int nev; bool timed;
 };
 
@@ -390,12 +388,6 @@ int stamp(Simp& s) {
 void drop_events(Simp& s) {
     for (int k = 0; k < s.nev; k++) (void)hipEventDestroy(s.ev[k]);
     s.nev = 0;
-}
-
-int read_u32(Simp& s, const uint32_t* dev, uint32_t* host, int n) {
-    if (hipMemcpyAsync(host, dev, 4 * (size_t)n, hipMemcpyDeviceToHost, s.st) != hipSuccess || hipStreamSynchronize(s.st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, s.what, hipGetLastError());
-    return 0;
 }
 
 // Rule 2: the grid, and the check that every finite vertex's cell index fits (the index is monotone in the coordinate, so the two corners
@@ -439,36 +431,27 @@ int build_clusters(Simp& s, int32_t* cluster, bool with_starts) {
         return stamp(s);
     }
     s.key64 = take<uint64_t>(s.alloc, s.user, V);
-    uint32_t* ka = take<uint32_t>(s.alloc, s.user, V);
-    uint32_t* va = take<uint32_t>(s.alloc, s.user, V);
-    uint32_t* kb = take<uint32_t>(s.alloc, s.user, V);
-    uint32_t* vb = take<uint32_t>(s.alloc, s.user, V);
-    uint32_t* head = take<uint32_t>(s.alloc, s.user, V + scan_scratch_u32(V));
-    void* scratch = s.alloc(s.user, radix_sort_scratch_bytes((size_t)V));
-    if (!s.key64 || !ka || !va || !kb || !vb || !head || !scratch) return api_fail(SURFEL_E_ALLOC, s.what);
-    hipLaunchKernelGGL(simp_key_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.verts, s.g, s.key64, ka, va);
+    SortPairs sp(s.alloc, s.user, V);
+    const ScanBuf head = take_scan(s.alloc, s.user, V);
+    if (!s.key64 || !sp.ok() || !head.flags) return api_fail(SURFEL_E_ALLOC, s.what);
+    hipLaunchKernelGGL(simp_key_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.verts, s.g, s.key64, sp.ka, sp.va);
     if (int rc = stamp(s)) return rc;
     // the 63-bit key as two stable LSD sorts of its 32-bit words; the key of a skipped vertex sets every bit of the high word
-    const uint64_t* key64 = s.key64;
-    hipStream_t st = s.st;
-    const uint32_t* order = sort_pairs_two_words(ka, va, kb, vb, V, 32, s.bits_hi, scratch, st, [&](const uint32_t* val, uint32_t* key) {
-        hipLaunchKernelGGL(simp_key_hi_kernel, dim3(grid(V)), dim3(ST), 0, st, V, key64, val, key);
-    });
-    if (!order) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
-    s.order = order;
-    uint32_t* sums = head + V;
-    const uint32_t* total = sums + scan_scratch_u32(V) - 1;
-    hipLaunchKernelGGL(simp_head_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, order, head);
-    scan_u32(head, V, sums, s.st);
+    if (sp.sort(32, s.st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
+    hipLaunchKernelGGL(simp_key_hi_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, sp.va, sp.ka);
+    if (sp.sort(s.bits_hi, s.st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
+    s.order = sp.va;
+    hipLaunchKernelGGL(simp_head_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, s.order, head.flags);
+    head.scan(s.st);
     uint32_t nc = 0;
     if (with_starts) {      // (the numbering needs the count to size cstart)
-        if (int rc = read_u32(s, total, &nc, 1)) return rc;
+        if (int rc = read_words(s.what, head.total, &nc, 1, s.st)) return rc;
         s.cstart = take<uint32_t>(s.alloc, s.user, (int64_t)nc + 1);
         if (!s.cstart) return api_fail(SURFEL_E_ALLOC, s.what);
     }
-    hipLaunchKernelGGL(simp_number_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, order, head, total, s.cluster, s.cstart);
+    hipLaunchKernelGGL(simp_number_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, s.order, head.flags, head.total, s.cluster, s.cstart);
     if (!with_starts)
-        if (int rc = read_u32(s, total, &nc, 1)) return rc;
+        if (int rc = read_words(s.what, head.total, &nc, 1, s.st)) return rc;
     s.nc = nc;
     if (int rc = launched("simp_number_kernel")) return rc;
     return stamp(s);
@@ -477,45 +460,34 @@ int build_clusters(Simp& s, int32_t* cluster, bool with_starts) {
 // Rule 7 up to the survivors: flags, candidates, three stable sorts, run heads, the scan of keep
 int dedupe_triangles(Simp& s) {
     const int64_t V = s.V, F = s.F;
-    s.valid = s.M = s.kept = 0; s.trip = nullptr; s.kpos = nullptr; s.ktotal = nullptr;
+    s.valid = s.M = s.kept = 0; s.trip = nullptr; s.keep = ScanBuf();
     if (F == 0 || s.nc == 0) return stamp(s);
-    uint32_t* flag = take<uint32_t>(s.alloc, s.user, F + scan_scratch_u32(F) + 1);
-    if (!flag) return api_fail(SURFEL_E_ALLOC, s.what);
-    uint32_t* fsums = flag + F;
-    uint32_t* ftotal = fsums + scan_scratch_u32(F) - 1;
-    uint32_t* tally = ftotal + 1;
+    const ScanBuf flag = take_scan(s.alloc, s.user, F, 1);
+    if (!flag.flags) return api_fail(SURFEL_E_ALLOC, s.what);
+    uint32_t* tally = flag.total + 1;      // the triangles that pass rule 1, behind the candidates' total
     if (hipMemsetAsync(tally, 0, 4, s.st) != hipSuccess) return api_fail(SURFEL_E_HIP, s.what, hipGetLastError());
-    hipLaunchKernelGGL(simp_tri_flag_kernel, dim3(grid(F)), dim3(ST), 0, s.st, F, V, s.tris, s.cluster, flag, tally);
-    scan_u32(flag, F, fsums, s.st);
+    hipLaunchKernelGGL(simp_tri_flag_kernel, dim3(grid(F)), dim3(ST), 0, s.st, F, V, s.tris, s.cluster, flag.flags, tally);
+    flag.scan(s.st);
     uint32_t host[2];      // candidates, triangles that pass rule 1 (adjacent words)
-    if (int rc = read_u32(s, ftotal, host, 2)) return rc;
+    if (int rc = read_words(s.what, flag.total, host, 2, s.st)) return rc;
     if (int rc = launched("simp_tri_flag_kernel")) return rc;
     const int64_t M = host[0];
     s.M = M; s.valid = host[1];
     if (M == 0) return stamp(s);
     s.trip = take<int32_t>(s.alloc, s.user, 3 * M);
-    uint32_t* ka = take<uint32_t>(s.alloc, s.user, M);
-    uint32_t* va = take<uint32_t>(s.alloc, s.user, M);
-    uint32_t* kb = take<uint32_t>(s.alloc, s.user, M);
-    uint32_t* vb = take<uint32_t>(s.alloc, s.user, M);
-    s.kpos = take<uint32_t>(s.alloc, s.user, M + scan_scratch_u32(M));
-    void* scratch = s.alloc(s.user, radix_sort_scratch_bytes((size_t)M));
-    if (!s.trip || !ka || !va || !kb || !vb || !s.kpos || !scratch) return api_fail(SURFEL_E_ALLOC, s.what);
-    hipLaunchKernelGGL(simp_cand_kernel, dim3(grid(F)), dim3(ST), 0, s.st, F, V, s.tris, s.cluster, flag, ftotal, s.trip, ka, va);
-    // (first, second, third cell) as three stable LSD sorts: third, second, first
-    const int bits = bit_length((uint64_t)(s.nc - 1)) > 0 ? bit_length((uint64_t)(s.nc - 1)) : 1;
+    SortPairs sp(s.alloc, s.user, M);
+    s.keep = take_scan(s.alloc, s.user, M);
+    if (!s.trip || !sp.ok() || !s.keep.flags) return api_fail(SURFEL_E_ALLOC, s.what);
+    hipLaunchKernelGGL(simp_cand_kernel, dim3(grid(F)), dim3(ST), 0, s.st, F, V, s.tris, s.cluster, flag.flags, flag.total, s.trip, sp.ka, sp.va);
+    // (first, second, third cell) as three stable LSD sorts: third, second, first, bit_length(nc - 1) bits each
     for (int word = 2; word >= 0; word--) {
-        if (word < 2) hipLaunchKernelGGL(simp_trip_key_kernel, dim3(grid(M)), dim3(ST), 0, s.st, M, s.trip, word, va, ka);
-        const int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)M, 0, bits, scratch, s.st);
-        if (r < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
-        if (r) { uint32_t* t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
+        if (word < 2) hipLaunchKernelGGL(simp_trip_key_kernel, dim3(grid(M)), dim3(ST), 0, s.st, M, s.trip, word, sp.va, sp.ka);
+        if (sp.sort(bit_length(s.nc - 1), s.st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
     }
-    uint32_t* ksums = s.kpos + M;
-    s.ktotal = ksums + scan_scratch_u32(M) - 1;
-    hipLaunchKernelGGL(simp_dup_kernel, dim3(grid(M)), dim3(ST), 0, s.st, M, s.trip, va, s.kpos);
-    scan_u32(s.kpos, M, ksums, s.st);
+    hipLaunchKernelGGL(simp_dup_kernel, dim3(grid(M)), dim3(ST), 0, s.st, M, s.trip, sp.va, s.keep.flags);
+    s.keep.scan(s.st);
     uint32_t kept = 0;
-    if (int rc = read_u32(s, s.ktotal, &kept, 1)) return rc;
+    if (int rc = read_words(s.what, s.keep.total, &kept, 1, s.st)) return rc;
     s.kept = kept;
     if (int rc = launched("simp_dup_kernel")) return rc;
     return stamp(s);
@@ -584,47 +556,34 @@ int surfel_simplify_mesh(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F
     int64_t nverts = 0;
     const int64_t nc = s.nc, M = s.M;
     hipStream_t st = s.st;
+    auto emit = [&]() -> int {      // compaction, then the sums and the solve
+        const int64_t n = 3 * F;
+        const ScanBuf used = take_scan(alloc, user, nc);
+        SortPairs sp(alloc, user, n);
+        uint32_t* ranges = take<uint32_t>(alloc, user, 2 * nc);
+        if (!used.flags || !sp.ok() || !ranges) return api_fail(SURFEL_E_ALLOC, s.what);
+        (void)hipMemsetAsync(used.flags, 0, (size_t)nc * 4, st);
+        hipLaunchKernelGGL(simp_used_kernel, dim3(grid(M)), dim3(ST), 0, st, M, s.trip, s.keep.flags, s.keep.total, used.flags);
+        used.scan(st);
+        hipLaunchKernelGGL(simp_tris_out_kernel, dim3(grid(M)), dim3(ST), 0, st, M, s.trip, s.keep.flags, s.keep.total, used.flags, tris_out);
+        uint32_t nv = 0;
+        if (int e = read_words(s.what, used.total, &nv, 1, st)) return e;
+        nverts = nv;
+        if (int e = launched("simp_tris_out_kernel")) return e;
+        if (int e = stamp(s)) return e;
+        // the (triangle, corner) incidences keyed by the corner's cell, one stable sort: a cell's incidences in ascending 3 t + corner
+        hipLaunchKernelGGL(simp_incidence_kernel, dim3(grid(F)), dim3(ST), 0, st, F, V, tris, s.cluster, (uint32_t)nc, sp.ka, sp.va);
+        if (sp.sort(bit_length(nc), st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");      // (nc itself keys the corners without a cell)
+        (void)hipMemsetAsync(ranges, 0, (size_t)nc * 8, st);
+        hipLaunchKernelGGL(simp_ranges_kernel, dim3(grid(n)), dim3(ST), 0, st, n, sp.ka, (uint32_t)nc, ranges, ranges + nc);
+        hipLaunchKernelGGL(simp_solve_kernel, dim3((unsigned)nc), dim3(SOLVE_T), 0, st, nc, V, s.g, lam, verts, colors, tris, s.key64, s.order, s.cstart,
+                           sp.va, ranges, ranges + nc, used.flags, used.total, cluster_vertex, verts_out, colors_out);
+        if (hipStreamSynchronize(st) != hipSuccess) return api_fail(SURFEL_E_HIP, s.what, hipGetLastError());
+        if (int e = launched("simp_solve_kernel")) return e;
+        return stamp(s);
+    };
     if (rc == 0 && s.kept > 0) {
-        uint32_t* upos = take<uint32_t>(alloc, user, nc + scan_scratch_u32(nc));
-        if (!upos) rc = api_fail(SURFEL_E_ALLOC, s.what);
-        if (rc == 0) {
-            uint32_t* usums = upos + nc;
-            const uint32_t* utotal = usums + scan_scratch_u32(nc) - 1;
-            (void)hipMemsetAsync(upos, 0, (size_t)nc * 4, st);
-            hipLaunchKernelGGL(simp_used_kernel, dim3(grid(M)), dim3(ST), 0, st, M, s.trip, s.kpos, s.ktotal, upos);
-            scan_u32(upos, nc, usums, st);
-            hipLaunchKernelGGL(simp_tris_out_kernel, dim3(grid(M)), dim3(ST), 0, st, M, s.trip, s.kpos, s.ktotal, upos, tris_out);
-            uint32_t nv = 0;
-            rc = read_u32(s, utotal, &nv, 1);
-            nverts = nv;
-            if (rc == 0) rc = launched("simp_tris_out_kernel");
-            if (rc == 0) rc = stamp(s);
-            // the (triangle, corner) incidences keyed by the corner's cell, one stable sort: a cell's incidences in ascending 3 t + corner
-            const int64_t n = 3 * F;
-            uint32_t* ka = take<uint32_t>(alloc, user, n);
-            uint32_t* va = take<uint32_t>(alloc, user, n);
-            uint32_t* kb = take<uint32_t>(alloc, user, n);
-            uint32_t* vb = take<uint32_t>(alloc, user, n);
-            uint32_t* ranges = take<uint32_t>(alloc, user, 2 * nc);
-            void* scratch = alloc(user, radix_sort_scratch_bytes((size_t)n));
-            if (rc == 0 && (!ka || !va || !kb || !vb || !ranges || !scratch)) rc = api_fail(SURFEL_E_ALLOC, s.what);
-            if (rc == 0) {
-                hipLaunchKernelGGL(simp_incidence_kernel, dim3(grid(F)), dim3(ST), 0, st, F, V, tris, s.cluster, (uint32_t)nc, ka, va);
-                const int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, bit_length((uint64_t)nc), scratch, st);
-                if (r < 0) rc = api_fail(SURFEL_E_LIMIT, "simplify: sort");
-                if (rc == 0) {
-                    const uint32_t* ks = r ? kb : ka;
-                    const uint32_t* vs = r ? vb : va;
-                    (void)hipMemsetAsync(ranges, 0, (size_t)nc * 8, st);
-                    hipLaunchKernelGGL(simp_ranges_kernel, dim3(grid(n)), dim3(ST), 0, st, n, ks, (uint32_t)nc, ranges, ranges + nc);
-                    hipLaunchKernelGGL(simp_solve_kernel, dim3((unsigned)nc), dim3(SOLVE_T), 0, st, nc, V, s.g, lam, verts, colors, tris, s.key64, s.order, s.cstart,
-                                       vs, ranges, ranges + nc, upos, utotal, cluster_vertex, verts_out, colors_out);
-                    if (hipStreamSynchronize(st) != hipSuccess) rc = api_fail(SURFEL_E_HIP, s.what, hipGetLastError());
-                    if (rc == 0) rc = launched("simp_solve_kernel");
-                    if (rc == 0) rc = stamp(s);
-                }
-            }
-        }
+        rc = emit();
     } else if (rc == 0) {      // no triangle survives: no vertex either
         if (cluster_vertex && nc > 0 && hipMemsetAsync(cluster_vertex, 0xFF, (size_t)nc * 4, st) != hipSuccess) rc = api_fail(SURFEL_E_HIP, s.what, hipGetLastError());
         if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = api_fail(SURFEL_E_HIP, s.what, hipGetLastError());

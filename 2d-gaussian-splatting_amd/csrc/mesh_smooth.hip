@@ -241,16 +241,7 @@ __global__ void __launch_bounds__(ST) smooth_step_kernel(int64_t V, const int32_
 using namespace surfel;
 
 namespace {
-
 inline unsigned grid(int64_t n) { return blocks_for(n, ST); }
-inline int bit_length(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
-
-int read_u32(const char* what, const uint32_t* dev, uint32_t* host, int n, hipStream_t st) {
-    if (hipMemcpyAsync(host, dev, 4 * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, what, hipGetLastError());
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -264,47 +255,38 @@ int64_t surfel_smooth_adjacency(surfel_alloc_fn alloc, void* user, int64_t V, in
         return api_fail(SURFEL_E_LIMIT, "smooth_adjacency: 2^31 or more vertices or directed vertex pairs (six per triangle)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t kept = 0, E2 = 0, tally[5] = {0, 0, 0, 0, 0};
+    ScanBuf keep;
     if (F > 0 && V > 0) {
-        uint32_t* keep = take<uint32_t>(alloc, user, F + scan_scratch_u32(F));
-        if (!keep) return api_fail(SURFEL_E_ALLOC, what);
-        uint32_t* ksums = keep + F;
-        const uint32_t* ktotal = ksums + scan_scratch_u32(F) - 1;
-        hipLaunchKernelGGL(smooth_keep_kernel, dim3(grid(F)), dim3(ST), 0, st, F, V, verts, tris, keep);
-        scan_u32(keep, F, ksums, st);
-        if (int rc = read_u32(what, ktotal, &kept, 1, st)) return rc;      // (the sort is sized by the kept triangles)
+        keep = take_scan(alloc, user, F);
+        if (!keep.flags) return api_fail(SURFEL_E_ALLOC, what);
+        hipLaunchKernelGGL(smooth_keep_kernel, dim3(grid(F)), dim3(ST), 0, st, F, V, verts, tris, keep.flags);
+        keep.scan(st);
+        if (int rc = read_words(what, keep.total, &kept, 1, st)) return rc;      // (the sort is sized by the kept triangles)
         if (int rc = launched("smooth_keep_kernel")) return rc;
-        if (kept > 0) {
-            const int64_t n = 6 * (int64_t)kept;
-            uint32_t* ka = take<uint32_t>(alloc, user, n);
-            uint32_t* va = take<uint32_t>(alloc, user, n);
-            uint32_t* kb = take<uint32_t>(alloc, user, n);
-            uint32_t* vb = take<uint32_t>(alloc, user, n);
-            uint32_t* head = take<uint32_t>(alloc, user, n + scan_scratch_u32(n));
-            uint32_t* esrc = take<uint32_t>(alloc, user, n);
-            uint32_t* estart = take<uint32_t>(alloc, user, n);
-            uint32_t* dtally = take<uint32_t>(alloc, user, 5);
-            void* scratch = alloc(user, radix_sort_scratch_bytes((size_t)n));
-            if (!ka || !va || !kb || !vb || !head || !esrc || !estart || !dtally || !scratch) return api_fail(SURFEL_E_ALLOC, what);
-            hipLaunchKernelGGL(smooth_emit_kernel, dim3(grid(F)), dim3(ST), 0, st, F, tris, keep, ktotal, ka, va);
-            // (src, dst) as two stable LSD sorts: the low word dst, the high word src, bit_length(V - 1) bits each
-            const int bits = bit_length((uint64_t)(V - 1)) > 0 ? bit_length((uint64_t)(V - 1)) : 1;
-            const uint32_t* order = sort_pairs_two_words(ka, va, kb, vb, n, bits, bits, scratch, st, [&](const uint32_t* val, uint32_t* key) {
-                hipLaunchKernelGGL(smooth_key_src_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, val, key);
-            });
-            if (!order) return api_fail(SURFEL_E_LIMIT, "smooth_adjacency: sort");
-            uint32_t* esums = head + n;
-            const uint32_t* etotal = esums + scan_scratch_u32(n) - 1;
-            hipLaunchKernelGGL(smooth_head_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, order, head);
-            scan_u32(head, n, esums, st);
-            hipLaunchKernelGGL(smooth_edge_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, order, head, etotal, esrc, neighbors, estart);
-            hipLaunchKernelGGL(smooth_mult_kernel, dim3(grid(n)), dim3(ST), 0, st, n, etotal, estart, multiplicity);
-            hipLaunchKernelGGL(smooth_rows_kernel, dim3(grid(V + 1)), dim3(ST), 0, st, V, etotal, esrc, offsets);
-            if (hipMemsetAsync(dtally, 0, sizeof(tally), st) != hipSuccess) return api_fail(SURFEL_E_HIP, what, hipGetLastError());
-            hipLaunchKernelGGL(smooth_flags_kernel, dim3(grid(V)), dim3(ST), 0, st, V, offsets, multiplicity, flags, dtally);
-            if (hipMemcpyAsync(tally, dtally, sizeof(tally), hipMemcpyDeviceToHost, st) != hipSuccess) return api_fail(SURFEL_E_HIP, what, hipGetLastError());
-            if (int rc = read_u32(what, etotal, &E2, 1, st)) return rc;
-            if (int rc = launched("smooth_flags_kernel")) return rc;
-        }
+    }
+    if (kept > 0) {
+        const int64_t n = 6 * (int64_t)kept;
+        SortPairs s(alloc, user, n);
+        const ScanBuf head = take_scan(alloc, user, n);
+        uint32_t* esrc = take<uint32_t>(alloc, user, n);
+        uint32_t* estart = take<uint32_t>(alloc, user, n);
+        uint32_t* dtally = take<uint32_t>(alloc, user, 5);
+        if (!s.ok() || !head.flags || !esrc || !estart || !dtally) return api_fail(SURFEL_E_ALLOC, what);
+        hipLaunchKernelGGL(smooth_emit_kernel, dim3(grid(F)), dim3(ST), 0, st, F, tris, keep.flags, keep.total, s.ka, s.va);
+        // (src, dst) as two stable LSD sorts: the low word dst, then the high word src, bit_length(V - 1) bits each
+        if (s.sort(bit_length(V - 1), st) < 0) return api_fail(SURFEL_E_LIMIT, "smooth_adjacency: sort");
+        hipLaunchKernelGGL(smooth_key_src_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, s.va, s.ka);
+        if (s.sort(bit_length(V - 1), st) < 0) return api_fail(SURFEL_E_LIMIT, "smooth_adjacency: sort");
+        hipLaunchKernelGGL(smooth_head_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, s.va, head.flags);
+        head.scan(st);
+        hipLaunchKernelGGL(smooth_edge_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, s.va, head.flags, head.total, esrc, neighbors, estart);
+        hipLaunchKernelGGL(smooth_mult_kernel, dim3(grid(n)), dim3(ST), 0, st, n, head.total, estart, multiplicity);
+        hipLaunchKernelGGL(smooth_rows_kernel, dim3(grid(V + 1)), dim3(ST), 0, st, V, head.total, esrc, offsets);
+        if (hipMemsetAsync(dtally, 0, sizeof(tally), st) != hipSuccess) return api_fail(SURFEL_E_HIP, what, hipGetLastError());
+        hipLaunchKernelGGL(smooth_flags_kernel, dim3(grid(V)), dim3(ST), 0, st, V, offsets, multiplicity, flags, dtally);
+        if (int rc = read_words(what, dtally, tally, 5, st, false)) return rc;
+        if (int rc = read_words(what, head.total, &E2, 1, st)) return rc;
+        if (int rc = launched("smooth_flags_kernel")) return rc;
     }
     if (kept == 0) {      // no edge: empty rows, every vertex isolated
         if (hipMemsetAsync(offsets, 0, (size_t)(V + 1) * 4, st) != hipSuccess ||

@@ -418,8 +418,7 @@ int surfel_texture_classify(surfel_alloc_fn alloc, void* user, int64_t V, int64_
     hipLaunchKernelGGL(texture_classify_kernel, dim3(blocks_for(F, CT)), dim3(CT), 0, st, V, F, verts, tris, density, cls, dcounts);
     if (int rc = launched("texture_classify_kernel")) return rc;
     uint32_t host[8];
-    if (hipMemcpyAsync(host, dcounts, sizeof(host), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, "texture_classify: counts", hipGetLastError());
+    if (int rc = read_words("texture_classify: counts", dcounts, host, 8, st)) return rc;
     for (int k = 0; k < TEX_CLASSES; k++) counts[k] = host[k];
     return 0;
 }
@@ -458,13 +457,13 @@ int64_t surfel_texture_layout(surfel_alloc_fn alloc, void* user, int64_t V, int6
     if (F == 0) return Ha;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n = (int64_t)TEX_CLASSES * F;
-    uint32_t* ind = take<uint32_t>(alloc, user, n + scan_scratch_u32(n));
-    if (!ind) return api_fail(SURFEL_E_ALLOC, "texture_layout", hipSuccess);
-    hipLaunchKernelGGL(texture_indicator_kernel, dim3(blocks_for(F, CT)), dim3(CT), 0, st, F, cls, ind);
+    const ScanBuf ind = take_scan(alloc, user, n);
+    if (!ind.flags) return api_fail(SURFEL_E_ALLOC, "texture_layout", hipSuccess);
+    hipLaunchKernelGGL(texture_indicator_kernel, dim3(blocks_for(F, CT)), dim3(CT), 0, st, F, cls, ind.flags);
     if (int rc = launched("texture_indicator_kernel")) return rc;
-    scan_u32(ind, n, ind + n, st);
+    ind.scan(st);
     if (int rc = launched("scan_u32")) return rc;
-    hipLaunchKernelGGL(texture_place_kernel, dim3(blocks_for(F, CT)), dim3(CT), 0, st, V, F, verts, tris, cls, ind, B, order, uv);
+    hipLaunchKernelGGL(texture_place_kernel, dim3(blocks_for(F, CT)), dim3(CT), 0, st, V, F, verts, tris, cls, ind.flags, B, order, uv);
     if (int rc = launched("texture_place_kernel")) return rc;
     return Ha;
 }

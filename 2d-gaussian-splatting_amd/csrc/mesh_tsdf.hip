@@ -421,7 +421,7 @@ int surfel_tsdf_init(surfel_tsdf_volume* v, surfel_alloc_fn alloc, void* user, v
     if (n >= ((int64_t)1 << 31) || surfel_tsdf_table_bytes(v) > v->budget_bytes)
         return api_fail(SURFEL_E_LIMIT, "tsdf_init: the dense block table exceeds the byte budget (raise the budget or the voxel size)");
     v->table = take<int32_t>(alloc, user, n);
-    v->scratch = take<uint32_t>(alloc, user, n + scan_scratch_u32(n));
+    v->scratch = take<uint32_t>(alloc, user, ScanBuf::words(n));
     if (!v->table || !v->scratch) return api_fail(SURFEL_E_ALLOC, "tsdf_init: allocator returned NULL");
     v->nblocks = 0; v->views = 0; v->nverts = v->ntris = 0;
     return hipMemsetAsync(v->table, 0xFF, (size_t)n * 4, static_cast<hipStream_t>(stream)) == hipSuccess ? 0
@@ -440,13 +440,11 @@ int64_t surfel_tsdf_allocate(surfel_tsdf_volume* v, surfel_alloc_fn alloc, void*
     if (!v || !v->table || !alloc || v->keys) return api_fail(SURFEL_E_INVALID, "tsdf_allocate: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n = table_n(v);
-    uint32_t* flags = v->scratch;
-    uint32_t* sums = v->scratch + n;
-    hipLaunchKernelGGL(mesh_flag_kernel, dim3(grid(n)), dim3(MT), 0, st, n, v->table, flags);
-    scan_u32(flags, n, sums, st);
+    const ScanBuf used(v->scratch, v->scratch + n, n);
+    hipLaunchKernelGGL(mesh_flag_kernel, dim3(grid(n)), dim3(MT), 0, st, n, v->table, used.flags);
+    used.scan(st);
     uint32_t nb = 0;
-    if (hipMemcpyAsync(&nb, sums + (scan_scratch_u32(n) - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, "tsdf_allocate: block count", hipGetLastError());
+    if (int rc = read_words("tsdf_allocate: block count", used.total, &nb, 1, st)) return rc;
     if ((int64_t)nb > MAX_BLOCKS)
         return api_fail(SURFEL_E_LIMIT, "tsdf_allocate: more blocks than 32-bit vertex / triangle indices can address (raise the voxel size)");
     if (surfel_tsdf_table_bytes(v) + (int64_t)nb * surfel_tsdf_block_bytes() > v->budget_bytes)
@@ -465,7 +463,7 @@ int64_t surfel_tsdf_allocate(surfel_tsdf_volume* v, surfel_alloc_fn alloc, void*
     v->pool_scratch = take<uint32_t>(alloc, user, scan_scratch_u32(nv));
     if (!v->keys || !v->stamp || !v->list || !v->tsdf_rgb || !v->weight || !v->info || !v->vbase || !v->tbase || !v->pool_scratch)
         return api_fail(SURFEL_E_ALLOC, "tsdf_allocate: allocator returned NULL");
-    hipLaunchKernelGGL(mesh_assign_kernel, dim3(grid(n)), dim3(MT), 0, st, n, v->table, flags, v->keys);
+    hipLaunchKernelGGL(mesh_assign_kernel, dim3(grid(n)), dim3(MT), 0, st, n, v->table, used.flags, v->keys);
     (void)hipMemsetAsync(v->stamp, 0, (size_t)nb * 4, st);
     (void)hipMemsetAsync(v->tsdf_rgb, 0, (size_t)nv * 16, st);
     (void)hipMemsetAsync(v->weight, 0, (size_t)nv * 4, st);
@@ -498,12 +496,11 @@ int surfel_tsdf_count(surfel_tsdf_volume* v, void* stream) {
     hipLaunchKernelGGL(mesh_classify_kernel, dim3((unsigned)v->nblocks), dim3(MT), 0, st, vo, v->keys, trgb, v->weight, v->info);
     hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)v->nblocks), dim3(MT), 0, st, vo, v->keys, trgb, v->weight, v->info, v->vbase, v->tbase);
     uint32_t tot[2];
-    const int64_t last = scan_scratch_u32(nv) - 1;
-    scan_u32(v->vbase, nv, v->pool_scratch, st);
-    if (hipMemcpyAsync(&tot[0], v->pool_scratch + last, 4, hipMemcpyDeviceToHost, st) != hipSuccess) return api_fail(SURFEL_E_HIP, "tsdf_count: copy");
-    scan_u32(v->tbase, nv, v->pool_scratch, st);      // (same stream: the copy above has read the vertex total)
-    if (hipMemcpyAsync(&tot[1], v->pool_scratch + last, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, "tsdf_count: copy", hipGetLastError());
+    const ScanBuf vb(v->vbase, v->pool_scratch, nv), tb(v->tbase, v->pool_scratch, nv);      // (one scratch for both scans)
+    vb.scan(st);
+    if (int rc = read_words("tsdf_count: copy", vb.total, &tot[0], 1, st, false)) return rc;
+    tb.scan(st);      // (same stream: the copy above has read the vertex total)
+    if (int rc = read_words("tsdf_count: copy", tb.total, &tot[1], 1, st)) return rc;
     v->nverts = tot[0]; v->ntris = tot[1];
     return launched("mesh_count_kernel");
 }
@@ -525,23 +522,17 @@ int surfel_mesh_clusters(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F
     const int64_t n = 3 * F;
     if (n >= ((int64_t)1 << 30) || V >= ((int64_t)1 << 31)) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: more than 2^30 triangle edges");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int bits = 1;      // key bits: ids 0 .. V - 1 and the key V of the edges with an id out of range
-    while (bits < 32 && ((int64_t)1 << bits) <= V) bits++;
-    uint32_t* ka = take<uint32_t>(alloc, user, n);
-    uint32_t* va = take<uint32_t>(alloc, user, n);
-    uint32_t* kb = take<uint32_t>(alloc, user, n);
-    uint32_t* vb = take<uint32_t>(alloc, user, n);
+    SortPairs s(alloc, user, n);
     int32_t* parent = take<int32_t>(alloc, user, F);
-    void* scratch = alloc(user, radix_sort_scratch_bytes((size_t)n));
-    if (!ka || !va || !kb || !vb || !parent || !scratch) return api_fail(SURFEL_E_ALLOC, "mesh_clusters: allocator returned NULL");
-    // (min, max) keys as two stable LSD sorts of 32-bit halves: max first, then min
-    hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, (uint32_t)V, tris, ka, va);
-    const uint32_t* vs = sort_pairs_two_words(ka, va, kb, vb, n, bits, bits, scratch, st, [&](const uint32_t* val, uint32_t* key) {
-        hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, val, key);
-    });
-    if (!vs) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
+    if (!s.ok() || !parent) return api_fail(SURFEL_E_ALLOC, "mesh_clusters: allocator returned NULL");
+    // (min, max) keys as two stable LSD sorts of 32-bit halves: max first, then min; bit_length(V) bits each, for the ids 0 .. V - 1
+    // and the key V of the edges with an id out of range
+    hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, (uint32_t)V, tris, s.ka, s.va);
+    if (s.sort(bit_length(V), st) < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
+    hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, s.va, s.ka);
+    if (s.sort(bit_length(V), st) < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
     hipLaunchKernelGGL(uf_init_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, size);
-    hipLaunchKernelGGL(uf_hook_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, vs, parent);
+    hipLaunchKernelGGL(uf_hook_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, s.va, parent);
     hipLaunchKernelGGL(uf_jump_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, label);
     hipLaunchKernelGGL(uf_size_kernel, dim3(grid(F)), dim3(MT), 0, st, F, label, size);
     return launched("uf_size_kernel");
@@ -556,24 +547,20 @@ int surfel_mesh_filter(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F, 
     if (V == 0 || F == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* vflag = take<uint32_t>(alloc, user, V);
-    uint32_t* vpos = take<uint32_t>(alloc, user, V);
     uint32_t* tflag = take<uint32_t>(alloc, user, F);
-    uint32_t* tpos = take<uint32_t>(alloc, user, F);
-    uint32_t* vs = take<uint32_t>(alloc, user, scan_scratch_u32(V));
-    uint32_t* ts = take<uint32_t>(alloc, user, scan_scratch_u32(F));
-    if (!vflag || !vpos || !tflag || !tpos || !vs || !ts) return api_fail(SURFEL_E_ALLOC, "mesh_filter: allocator returned NULL");
+    const ScanBuf vpos = take_scan(alloc, user, V), tpos = take_scan(alloc, user, F);
+    if (!vflag || !tflag || !vpos.flags || !tpos.flags) return api_fail(SURFEL_E_ALLOC, "mesh_filter: allocator returned NULL");
     (void)hipMemsetAsync(vflag, 0, (size_t)V * 4, st);
     hipLaunchKernelGGL(filter_mark_kernel, dim3(grid(F)), dim3(MT), 0, st, V, F, tris, label, size, threshold, tflag, vflag);
-    hipLaunchKernelGGL(copy_flags_kernel, dim3(grid(V)), dim3(MT), 0, st, V, vflag, vpos);
-    hipLaunchKernelGGL(copy_flags_kernel, dim3(grid(F)), dim3(MT), 0, st, F, tflag, tpos);
-    scan_u32(vpos, V, vs, st);
-    scan_u32(tpos, F, ts, st);
-    hipLaunchKernelGGL(filter_verts_kernel, dim3(grid(V)), dim3(MT), 0, st, V, vflag, vpos, verts, colors, verts_out, colors_out);
-    hipLaunchKernelGGL(filter_tris_kernel, dim3(grid(F)), dim3(MT), 0, st, F, tflag, tpos, tris, vpos, tris_out);
+    hipLaunchKernelGGL(copy_flags_kernel, dim3(grid(V)), dim3(MT), 0, st, V, vflag, vpos.flags);
+    hipLaunchKernelGGL(copy_flags_kernel, dim3(grid(F)), dim3(MT), 0, st, F, tflag, tpos.flags);
+    vpos.scan(st);
+    tpos.scan(st);
+    hipLaunchKernelGGL(filter_verts_kernel, dim3(grid(V)), dim3(MT), 0, st, V, vflag, vpos.flags, verts, colors, verts_out, colors_out);
+    hipLaunchKernelGGL(filter_tris_kernel, dim3(grid(F)), dim3(MT), 0, st, F, tflag, tpos.flags, tris, vpos.flags, tris_out);
     uint32_t tot[2];
-    if (hipMemcpyAsync(&tot[0], vs + scan_scratch_u32(V) - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&tot[1], ts + scan_scratch_u32(F) - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return api_fail(SURFEL_E_HIP, "mesh_filter: copy", hipGetLastError());
+    if (int rc = read_words("mesh_filter: copy", vpos.total, &tot[0], 1, st, false)) return rc;
+    if (int rc = read_words("mesh_filter: copy", tpos.total, &tot[1], 1, st)) return rc;
     counts_out[0] = tot[0]; counts_out[1] = tot[1];
     return launched("filter_tris_kernel");
 }

@@ -25,19 +25,47 @@ inline unsigned blocks_for(int64_t n, int64_t per_block) { return (unsigned)((n 
 template <class T>
 T* take(surfel_alloc_fn alloc, void* user, int64_t n) { return static_cast<T*>(alloc(user, (size_t)(n > 0 ? n : 1) * sizeof(T))); }
 
-// A 64-bit key as two stable LSD sorts of its 32-bit words.  (ka, va) hold the low words and the values; after the first sort
-// fill_hi(vals_sorted, keys_out) launches the caller's kernel that writes every sorted slot's high word.  Returns the value buffer of
-// the final order (va or vb), or nullptr when a sort fails.
-template <class F>
-const uint32_t* sort_pairs_two_words(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, int64_t n, int bits_lo, int bits_hi, void* scratch,
-                                     hipStream_t st, F fill_hi) {
-    int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, bits_lo, scratch, st);
-    if (r < 0) return nullptr;
-    if (r) { uint32_t* t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
-    fill_hi(va, ka);
-    r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, bits_hi, scratch, st);
-    if (r < 0) return nullptr;
-    return r ? vb : va;
+inline int bit_length(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
+
+// n 32-bit words device -> host on st, then the wait for the stream; wait = false leaves the wait to the next read
+inline int read_words(const char* what, const void* dev, void* host, int64_t n, hipStream_t st, bool wait = true) {
+    if (hipMemcpyAsync(host, dev, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || (wait && hipStreamSynchronize(st) != hipSuccess))
+        return api_fail(SURFEL_E_HIP, what, hipGetLastError());
+    return 0;
 }
+
+// n flags and the words scan_u32 needs for them: scan() turns the flags into exclusive positions in place and leaves their sum in *total
+struct ScanBuf {
+    uint32_t* flags = nullptr; uint32_t* sums = nullptr; uint32_t* total = nullptr;
+    int64_t n = 0;
+    ScanBuf() = default;
+    ScanBuf(uint32_t* f, uint32_t* s, int64_t n_) : flags(f), sums(s), total(s + scan_scratch_u32(n_) - 1), n(n_) {}
+    static int64_t words(int64_t n) { return n + scan_scratch_u32(n); }      // flags | sums, as take_scan lays them out
+    void scan(hipStream_t st) const { scan_u32(flags, n, sums, st); }
+};
+
+// one allocation: flags[n] | sums | extra_words behind the total (at total + 1); flags is null when the allocator fails
+inline ScanBuf take_scan(surfel_alloc_fn alloc, void* user, int64_t n, int64_t extra_words = 0) {
+    uint32_t* p = take<uint32_t>(alloc, user, ScanBuf::words(n) + extra_words);
+    return p ? ScanBuf(p, p + n, n) : ScanBuf();
+}
+
+// Two key / value buffer pairs for n pairs and the sort's scratch.  The caller fills (ka, va); after sort() (ka, va) name the sorted
+// pairs, whichever buffers the last pass wrote.
+struct SortPairs {
+    uint32_t *ka, *va, *kb, *vb;
+    void* scratch;
+    int64_t n;
+    SortPairs(surfel_alloc_fn alloc, void* user, int64_t n_)
+        : ka(take<uint32_t>(alloc, user, n_)), va(take<uint32_t>(alloc, user, n_)), kb(take<uint32_t>(alloc, user, n_)),
+          vb(take<uint32_t>(alloc, user, n_)), scratch(alloc(user, radix_sort_scratch_bytes((size_t)n_))), n(n_) {}
+    bool ok() const { return ka && va && kb && vb && scratch; }
+    // stable, on key bits [0, bits), bits held to 1 .. 32; negative when the sort fails
+    int sort(int bits, hipStream_t st) {
+        const int r = radix_sort_pairs_u32(ka, va, kb, vb, (size_t)n, 0, bits < 1 ? 1 : bits > 32 ? 32 : bits, scratch, st);
+        if (r > 0) { uint32_t* t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
+        return r < 0 ? r : 0;
+    }
+};
 
 }  // namespace surfel

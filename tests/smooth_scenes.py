@@ -87,4 +87,8 @@ def meshes():
     cases = {"cube": noisy_cube(), "sphere": (sv, st), "special": S.special_cube(), "plates": noisy_plates(), "clustered": clustered_plates(),
              "fan": fan(), "umbrellas": umbrellas()[:2], "no-vertex": (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)),
              "no-triangle": (noisy_cube()[0][:300], np.zeros((0, 3), np.int32)), "all-dropped": all_dropped()}
+    # the scans' edges: 4 096 triangles are one full scan tile of keep flags and six full tiles of half-edges; one triangle is a scan of
+    # one flag, and its three vertices make each sort a single pass, which leaves the sorted pairs in the second buffer pair
+    cases["fan-one-tile"] = fan(rim=4097)
+    cases["one-triangle"] = (noisy_cube()[0][:3], np.array([[0, 1, 2]], np.int32))
     return cases

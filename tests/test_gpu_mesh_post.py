@@ -375,6 +375,28 @@ def test_marching_cubes_crafted_fields(mc_volume, kind):
     assert dc < 1e-5
 
 
+@pytest.mark.parametrize("origin,dims", [((-1, 0, 0), (1, 1, 1)), ((-8, -8, -8), (16, 16, 16)), ((-8, -120, 0), (17, 241, 1))])
+def test_allocate_scan_tile_edges(origin, dims):
+    """The allocation scans one flag per table entry: tables of one entry, of one full scan tile (4 096) and of one entry more.  The blocks
+    found are the oracle's in table order.  The table of one block also gives the extraction its shortest scan, one tile of voxels."""
+    import surfel_mesh
+    dev = torch.device(DEV)
+    vol = surfel_mesh.TsdfVolume(MC_VS, MC_TR, origin, dims, 1 << 30, dev)
+    for d, cam in _mc_views():
+        vol.mark(torch.from_numpy(d).to(dev), torch.from_numpy(cam).to(dev))
+    vol.allocate()
+    want = np.array([b for b in _mc_blocks() if all(o <= x < o + n for x, o, n in zip(b, origin, dims))], np.int64)
+    coords = vol.blocks()[0]
+    assert len(want) == {1: 1, 4096: 8, 4097: 4}[int(np.prod(dims))] and np.array_equal(coords, want)
+    if len(want) == 1:
+        tsdf, w, rgb = _mc_field("normal", 4096)
+        vol._tensor("tsdf_rgb", torch.float32, (4096, 4)).copy_(torch.from_numpy(np.concatenate([tsdf[:, None], rgb], 1)))
+        vol._tensor("weight", torch.float32, (4096,)).copy_(torch.from_numpy(w))
+        verts, _, tris = O.marching_cubes(coords, tsdf.astype(np.float64), w.astype(np.float64), rgb.astype(np.float64), MC_VS)
+        mesh = vol.extract()
+        assert len(tris) > 1000 and mesh.vertices.shape[0] == len(verts) and np.array_equal(mesh.triangles.cpu().numpy(), tris)
+
+
 # ------------------------------------------------------------------------------------------------ fusion edges
 FU_VS, FU_TR, FU_DT = 0.03, 0.12, 10.0
 FU_W, FU_H = 64, 48

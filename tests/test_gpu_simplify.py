@@ -52,6 +52,17 @@ def _cases():
     cases["plates"] = (pv, pt, None, S.PLATE_CELL, S.PLATE_ORIGIN)
     cases["cube-fine"] = (cv, ct, None, O.grid_cell(cv, 81), None)
     cases["cube-moved-origin"] = (cv, ct, None, np.float32(0.3), np.array([-1.25, -1.0, -1.5], np.float32))
+    # the scans' edges.  A 64 x 64 lattice, every point the centre of its own cell, with its first 4 096 triangles: vertices, triangles,
+    # candidates and cells are one full scan tile each.  One triangle over three cells: scans of one flag, and two key bits, so that each
+    # of the three sorts is a single pass and leaves the sorted pairs in the second buffer pair.
+    g = np.arange(64)
+    X, Y = np.meshgrid(g, g, indexing="ij")
+    lv = np.stack([X.reshape(-1) / 16.0, Y.reshape(-1) / 16.0, np.zeros(4096)], 1).astype(np.float32)
+    a, b = (x.reshape(-1) for x in np.meshgrid(np.arange(63), np.arange(63), indexing="ij"))
+    at = lambda u, w: u * 64 + w
+    lt = np.concatenate([np.stack([at(a, b), at(a + 1, b), at(a + 1, b + 1)], 1), np.stack([at(a, b), at(a + 1, b + 1), at(a, b + 1)], 1)])[:4096].astype(np.int32)
+    cases["lattice-one-tile"] = (lv, lt, None, S.PLATE_CELL, S.PLATE_ORIGIN)
+    cases["one-triangle"] = (lv[[0, 1, 64]], np.array([[0, 1, 2]], np.int32), None, S.PLATE_CELL, S.PLATE_ORIGIN)
     return cases
 
 
@@ -102,6 +113,18 @@ def test_device_equals_the_restatement_bit_for_bit(name):
     assert counted == {k: want[4][k] for k in STAT_KEYS if k != "vertices"}
     b = P.mesh_bounds(_t(v))
     assert np.array_equal(b[0], O.bounds(v)[0]) and np.array_equal(b[1], O.bounds(v)[1])
+
+
+def test_scan_edge_cases_hold_what_they_are_there_for():
+    """conditions on the inputs of lattice-one-tile and one-triangle, and the one count they cannot reach: a single vertex"""
+    import surfel_simplify as P
+    v, t, _, cell, origin = CASES["lattice-one-tile"]
+    w = _want("lattice-one-tile")[4]
+    assert len(v) == len(t) == 4096 and w["clusters"] == 4096 and w["dropped"] == w["collapsed"] == w["duplicates"] == 0 and w["triangles"] == 4096
+    w = _want("one-triangle")[4]
+    assert w["clusters"] == 3 and w["triangles"] == 1
+    got = P.vertex_clusters(_mesh(v[:1], np.zeros((0, 3), np.int32)), float(cell), origin)
+    assert got.cpu().numpy().tolist() == [0]
 
 
 # ------------------------------------------------------------------------------------------------ 2: the same bytes

@@ -81,6 +81,15 @@ def test_layout_equals_the_restatement_bit_for_bit(name, density):
     print("%s at %g: classes %s, atlas %d x %d" % (name, density, a.counts, a.width, a.height))
 
 
+@pytest.mark.parametrize("F", [1, 2048])
+def test_layout_at_the_scan_edges(F):
+    """The layout scans six indicator words per triangle: one triangle is the shortest scan there is, 2 048 triangles are three full scan
+    tiles of 4 096 (no count gives one tile exactly, 4 096 is no multiple of six)."""
+    v, t = S.cube()
+    density = S.CUBE_DENSITIES[0]
+    _same_layout(_device_layout(v, t[:F], density, S.WA), O.layout(v, t[:F], density, S.WA))
+
+
 # ------------------------------------------------------------------------------------------------ 2: the bake
 def _bake_scene():
     """the ellipsoid, its device layout and the device's own depth images of the 24 arc views, computed once"""

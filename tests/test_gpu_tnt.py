@@ -92,6 +92,9 @@ def _voxel_cases():
     yield "one point", np.array([[1.5, -2.0, 3.0]], np.float32), 0.25
     yield "empty", np.zeros((0, 3), np.float32), 0.25
     yield "100 000 points in one cell", (rng.uniform(0, 1, size=(100000, 3)) * 0.01 + [5.0, 6.0, -7.0]).astype(np.float32), 1.0
+    # the run heads are scanned over n + 1 elements (the last one holds the cell count): one full scan tile of 4 096, and one element more
+    yield "4 095 points", rng.uniform(-1, 1, size=(4095, 3)).astype(np.float32), 0.1
+    yield "4 096 points", rng.uniform(-1, 1, size=(4096, 3)).astype(np.float32), 0.1
 
 
 def test_voxel_down_sample_matches_the_oracle():
