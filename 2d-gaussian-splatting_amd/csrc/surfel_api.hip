@@ -319,9 +319,18 @@ int higher_msb(uint32_t n) {   // number of bits needed to represent values < n
     return b < 1 ? 1 : b;
 }
 
-// per-tile depth sort (1) or depth-presorted emission (0) for R instances: bitonic work grows as n log^2 n — at ~1100 instances per
-// tile it costs 0.25 ms vs 0.15 ms for the P-sized radix sort (C4)
-int per_tile_pays(int64_t R, int gx, int gy) { return R <= (int64_t)640 * gx * gy ? 1 : 0; }
+// per-tile depth sort (1) or depth-presorted emission (0) for R instances of P surfels, from frame sizes alone.  The per-tile path saves
+// the P-sized depth sort and the scan through its order — 0.057 ms per million surfels, and never less than the 0.07 ms the four
+// look-back passes cost below 2^20 keys — and pays the per-tile sorter: 0.013 - 0.017 ms per million instances once runs are long enough
+// for its radix classes (the register network, n log^2 n, is left to runs of <= 512).  Break-even near R = 4.2 max(P, 2^20); measured
+// (profiles/r09_pertile_budget.jsonl, binning stages presorted / per-tile): garden R = 3.2 P 0.342 / 0.309 ms, C2H R = 9.7 P at
+// P = 0.3 M 0.173 / 0.151, C4 R = 3.7 P 0.322 / 0.322 (stays presorted), C5 R = 12 P with every fifth run beyond the LDS capacity
+// 3.13 / 4.85.  Frames of <= 640 instances per tile take the per-tile path as before.
+int per_tile_pays(int64_t R, int P, int gx, int gy) {
+    const int64_t tiles = (int64_t)gx * gy, Pf = P > (1 << 20) ? P : (1 << 20);
+    if (R <= 640 * tiles) return 1;
+    return (2 * R <= 7 * Pf && R <= 2048 * tiles) ? 1 : 0;
+}
 
 int alloc_bin(size_t n, size_t sort_bytes, bool stream, surfel_alloc_fn binning_alloc, void* binning_user, BinState* bin) {
     const bool strm = stream && BinState::wants_stream(n);
@@ -364,7 +373,7 @@ int64_t bin_exact(const PreprocessArgs& pa, int end_bit, int per_tile, int64_t R
                   StageTimer& tm, hipStream_t s) {
     if (per_tile < 0 && R < 0) {         // first frame of this size: wait for R now (loses the host/device overlap once)
         HIP_TRY(hipEventSynchronize(evR));
-        per_tile = per_tile_pays(pinned_total(hR, false), pa.gx, pa.gy);
+        per_tile = per_tile_pays(pinned_total(hR, false), pa.P, pa.gx, pa.gy);
     }
     tm.begin();
     const uint32_t* order = geom.ord_a;      // identity (written by preprocess)
@@ -465,6 +474,22 @@ int surfel_debug_sort_pairs(surfel_alloc_fn scratch_alloc, void* scratch_user, u
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+int surfel_debug_tile_depth_sort(int ntiles, int64_t n, uint32_t* ranges, uint32_t* point_list, const uint32_t* depth_keys, uint32_t* scratch,
+                                 int decode, void* stream) {
+    if (ntiles < 0 || n < 0 || n >= ((int64_t)1 << 32) || (ntiles > 0 && !ranges) || (n > 0 && (!point_list || !depth_keys || !scratch)))
+        return fail(SURFEL_E_INVALID, "bad arguments");
+    if (ntiles == 0) return 0;
+    launch_tile_depth_sort(ntiles, n, reinterpret_cast<uint2*>(ranges), point_list, depth_keys, scratch, scratch + n, scratch + 2 * n, decode != 0,
+                           static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int surfel_debug_tile_depth_sort_classes(int* out, int cap) {
+    if (!out || cap < 0) return fail(SURFEL_E_INVALID, "bad arguments");
+    return tile_depth_sort_classes(out, cap);
+}
+int surfel_debug_set_tile_radix_min(int longest_network_run) { set_tile_radix_min(longest_network_run); return 0; }
 
 int surfel_set_option(const char* name, int value) {
     if (name && std::strcmp(name, "cull") == 0) { g_opt_cull = value ? 1 : 0; return 0; }
@@ -640,7 +665,7 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
         //    bin_exact sizes them exactly, after a host wait for R.
         const int end_bit = higher_msb((uint32_t)(gx * gy));
         int per_tile = opt_tile_sort == 2 ? 1 : (opt_tile_sort == 0 ? 0 : -1);
-        if (per_tile < 0 && g_th.last_R >= 0 && g_th.last_W == width && g_th.last_H == height) per_tile = per_tile_pays(g_th.last_R, gx, gy);
+        if (per_tile < 0 && g_th.last_R >= 0 && g_th.last_W == width && g_th.last_H == height) per_tile = per_tile_pays(g_th.last_R, P, gx, gy);
         const int64_t cap = (opt_capacity && per_tile == 1 && debug != 1) ? ce->capacity(end_bit) : 0;
         if (cap > 0) {      // the binning buffers exist before preprocess runs: it clears the tile sort's head on the way
             if (int e = alloc_bin((size_t)cap, capacity_sort_scratch_bytes((size_t)cap, end_bit), opt_stream, binning_alloc, binning_user, &bin)) return e;

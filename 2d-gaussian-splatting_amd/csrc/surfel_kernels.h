@@ -99,7 +99,10 @@ int radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, u
                          void* scratch, hipStream_t s, bool head_zeroed = false);
 size_t radix_sort_head_words(size_t n);       // words at the start of the sort scratch that must be zero (head_zeroed callers)
 size_t scan_scratch_words(size_t n);          // zeroed scratch of launch_scan_gather
-// decode: the ranges come from the sort's last pass (radix_sort_pairs_u32_devn) with complemented starts; the kernel turns them back
+// decode: the ranges come from the sort's last pass (radix_sort_pairs_u32_devn) with complemented starts; the kernel turns them back.
+// Every run must arrive in ascending surfel index (its radix classes are stable sorts on the depth bits alone).  tmp_*: R words each.
+int tile_depth_sort_classes(int* out, int cap);      // size classes (see surfel_sort.hip); returns how many there are
+void set_tile_radix_min(int v);                      // longest run the register network takes (measurement; < 0: the default)
 void launch_tile_depth_sort(int ntiles, int64_t R, uint2* ranges, uint32_t* point_list, const uint32_t* depth_keys, uint32_t* tmp_ids,
                             uint32_t* tmp_keys, uint32_t* tmp_rank, bool decode, hipStream_t s);
 void launch_scan_gather(const uint32_t* vals, const uint32_t* order, int packed, uint32_t* out, size_t n, void* zeroed_scratch, hipStream_t s);

@@ -420,8 +420,10 @@ void launch_scan_gather(const uint32_t* vals, const uint32_t* order, int packed,
 // Small / medium frames (the BASELINE configs[1] regime): instead of depth-sorting all P surfels before emission (4 radix
 // passes, ~16 us each because they are look-back-latency-bound, not byte-bound), instances are emitted in surfel-index order,
 // grouped by the stable tile sort, and every tile then orders ITS OWN run by (float depth bits, surfel index) — the same total
-// order the depth-presorted path produces — with a bitonic network in LDS: one launch, all tiles in parallel.
-// Tiles with more than TS_CAP instances take a (slow, rare) chunked rank sort through global scratch.
+// order the depth-presorted path produces: one launch, all tiles in parallel.  Short runs (<= 512) take a bitonic network in
+// registers, longer ones a stable LSD radix sort in LDS, runs beyond the LDS capacity the same passes streamed through global scratch.
+// With the radix classes the cost is linear in the run, and large frames whose instance count is small against their surfel count
+// take this path too (per_tile_pays, surfel_api.hip).
 
 // Bitonic network over 256*E keys held E per thread in registers (element index = e*256 + tid): partners 256 or more apart are
 // another register of the same thread, partners closer than a wave come by lane shuffle, only distances 64 / 128 go through
@@ -479,13 +481,196 @@ __device__ __forceinline__ void tile_sort_regs(uint32_t n, uint32_t* __restrict_
     }
 }
 
-// TS_CAP = largest run sorted by the LDS network (8 B of LDS per key: 2048 -> 16 KB -> 10 workgroups / CU for frames whose tiles
-// are small; 4096 -> 32 KB otherwise).
+// ---- per-tile LSD radix sort (runs longer than the network pays for) ----------------------------------------------------------
+// PRECONDITION: the run arrives in ascending surfel index (surfel-order emission, then the stable tile sort: bin_exact with per_tile,
+// bin_capacity), so a STABLE sort on the 32 depth bits alone leaves it ordered by (depth bits, surfel index) — what the network gets
+// by comparing the index explicitly.  Passes of 8 bits, ranked with the wave64 match-by-ballot of os_pass_fat_kernel; a pass whose
+// eight bits are the same in every key of the run (OR == AND) is skipped: the top byte of depths in [0.2, far) nearly always is.
+constexpr int TR_WAVES = RS_THREADS / 64;
+constexpr int TR_BITONIC_MAX = 8 * RS_THREADS;      // longest run the register network is built for
+constexpr int TR_RADIX_MIN = 2 * RS_THREADS;        // runs up to here stay with the network (measured: profiles/r09_tile_sort_classes.jsonl)
+constexpr int TR_CHUNK_IPT = 8;                     // chunked form: 2048 items per chunk
+int g_tile_radix_min = TR_RADIX_MIN;
+void set_tile_radix_min(int v) { g_tile_radix_min = v < 0 ? TR_RADIX_MIN : (v > TR_BITONIC_MAX ? TR_BITONIC_MAX : v); }
+
+// rank of this lane's item among the items with digit d the wave has ranked so far (cnt_row: the wave's own 256 counters)
+__device__ __forceinline__ uint32_t tr_rank(uint32_t d, bool valid, uint32_t* cnt_row) {
+    unsigned long long mm = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < RS_BITS; b++) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long bal = __ballot(bit);
+        mm &= bit ? bal : ~bal;
+    }
+    if (!valid) mm = 0ull;
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+    const uint32_t prev = valid ? cnt_row[d] : 0u;      // same-wave LDS ops are program-ordered
+    if (valid && below == 0) cnt_row[d] = prev + (uint32_t)__popcll(mm);
+    return prev + below;
+}
+
+// OR and AND of a value over the workgroup (s_w: 2 * TR_WAVES words; ends behind a barrier)
+__device__ __forceinline__ uint32_t tr_key_spread(uint32_t o, uint32_t a, uint32_t* s_w, int lane, int wave) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { o |= __shfl_xor(o, off); a &= __shfl_xor(a, off); }
+    if (lane == 0) { s_w[wave] = o; s_w[TR_WAVES + wave] = a; }
+    __syncthreads();
+    o = 0u; a = ~0u;
+#pragma unroll
+    for (int w = 0; w < TR_WAVES; w++) { o |= s_w[w]; a &= s_w[TR_WAVES + w]; }
+    return o ^ a;      // bits in which the keys differ
+}
+
+// exclusive scan of one count per thread (thread = digit) over the workgroup (s_w: TR_WAVES words; one barrier inside)
+__device__ __forceinline__ uint32_t tr_digit_scan(uint32_t cnt, uint32_t* s_w, int lane, int wave) {
+    uint32_t x = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o); if (lane >= o) x += y; }
+    if (lane == 63) s_w[wave] = x;
+    __syncthreads();
+    uint32_t excl = x - cnt;
+    for (int w = 0; w < wave; w++) excl += s_w[w];
+    return excl;
+}
+
+// n <= 256 * IPT items, the whole run in LDS: wave w holds items [w * 64 * ipt, (w + 1) * 64 * ipt) in registers (ipt = ceil(n / 256):
+// all four waves stay busy on a run that does not fill the class), a pass scatters them into s_item in sorted order and reads them back.
+// The run is padded to 256 * ipt items with key 0xffffffff: the padding starts behind the run and no stable pass moves it in front of a
+// real item, so the first n items are the run at every moment and no step needs a validity mask.
+template <int IPT>
+__device__ __forceinline__ void tile_radix_lds(uint32_t n, uint32_t* __restrict__ pl, const uint32_t* __restrict__ depth_keys,
+                                               uint32_t (*s_cnt)[RS_RADIX], uint2* s_item, uint32_t* s_w, uint32_t tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint32_t ipt = (n + RS_THREADS - 1) / RS_THREADS;
+    const uint32_t wbase = (uint32_t)wave * 64u * ipt;
+    uint32_t k[IPT], v[IPT], rank[IPT];
+    uint32_t o = 0u, a = ~0u;
+#pragma unroll
+    for (int it = 0; it < IPT; it++) {
+        const uint32_t idx = wbase + (uint32_t)it * 64u + lane;
+        // (no assignment under a branch: the compiler keeps these arrays as one 16-register tuple and copies all of it at every such join)
+        const bool ok = (uint32_t)it < ipt && idx < n;
+        const uint32_t id = pl[ok ? idx : 0u], key = depth_keys[id];
+        v[it] = id; k[it] = ok ? key : 0xffffffffu; rank[it] = 0u;      // (it >= ipt: never ranked or stored)
+        o |= ok ? key : 0u; a &= ok ? key : 0xffffffffu;
+    }
+    for (int j = lane; j < RS_RADIX; j += 64) s_cnt[wave][j] = 0u;
+    const uint32_t diff = tr_key_spread(o, a, s_w, lane, wave);
+    if (diff == 0u) return;      // all keys equal: the run is in order
+#pragma unroll 1
+    for (int shift = 0; shift < 32; shift += RS_BITS) {
+        if (((diff >> shift) & (RS_RADIX - 1u)) == 0u) continue;      // (the same in every thread of the workgroup)
+#pragma unroll
+        for (int it = 0; it < IPT; it++) {
+            uint32_t r = 0u;
+            if ((uint32_t)it < ipt) r = tr_rank((k[it] >> shift) & (RS_RADIX - 1u), true, s_cnt[wave]);
+            rank[it] = r;
+            __builtin_amdgcn_sched_barrier(0);      // one item's ballots at a time
+        }
+        __syncthreads();
+        uint32_t cw[TR_WAVES], cnt = 0;      // thread = digit
+#pragma unroll
+        for (int w = 0; w < TR_WAVES; w++) { cw[w] = s_cnt[w][tid]; cnt += cw[w]; }
+        uint32_t run = tr_digit_scan(cnt, s_w + 2 * TR_WAVES, lane, wave);
+#pragma unroll
+        for (int w = 0; w < TR_WAVES; w++) { s_cnt[w][tid] = run; run += cw[w]; }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < IPT; it++) {
+            if ((uint32_t)it < ipt) s_item[s_cnt[wave][(k[it] >> shift) & (RS_RADIX - 1u)] + rank[it]] = make_uint2(k[it], v[it]);      // < 256 ipt <= TS_CAP
+        }
+        for (int j = lane; j < RS_RADIX; j += 64) s_cnt[wave][j] = 0u;      // the wave's own row, behind its own reads
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < IPT; it++) {
+            const uint32_t idx = wbase + (uint32_t)it * 64u + lane;
+            const uint2 kv = s_item[(uint32_t)it < ipt ? idx : 0u];
+            k[it] = kv.x; v[it] = kv.y;
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < IPT; it++) {
+        const uint32_t idx = wbase + (uint32_t)it * 64u + lane;
+        if ((uint32_t)it < ipt && idx < n) pl[idx] = v[it];
+    }
+}
+
+// Runs beyond the LDS capacity: the same passes with the run streamed in chunks of 2048 items between two (key, id) buffer pairs in
+// global memory — (ak, pl) and (bk, bv), all slices of this tile alone.  One sweep gathers the keys and counts the digits of all four
+// passes in LDS; a pass then hands every chunk its digits' next free slots (s_base) in chunk order, which keeps it stable.
+__device__ __forceinline__ void tile_radix_chunked(uint32_t n, uint32_t* pl, const uint32_t* __restrict__ depth_keys, uint32_t* ak,
+                                                   uint32_t* bk, uint32_t* bv, uint32_t (*s_cnt)[RS_RADIX], uint32_t (*s_hist)[RS_RADIX],
+                                                   uint32_t* s_base, uint32_t* s_w, uint32_t tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int p = 0; p < RS_MAX_PASSES; p++) s_hist[p][tid] = 0u;
+    for (int j = lane; j < RS_RADIX; j += 64) s_cnt[wave][j] = 0u;
+    __syncthreads();
+    uint32_t o = 0u, a = ~0u;
+    for (uint32_t i = tid; i < n; i += RS_THREADS) {
+        const uint32_t key = depth_keys[pl[i]];
+        ak[i] = key; o |= key; a &= key;
+#pragma unroll
+        for (int p = 0; p < RS_MAX_PASSES; p++) atomicAdd(&s_hist[p][(key >> (p * RS_BITS)) & (RS_RADIX - 1u)], 1u);      // (LDS)
+    }
+    const uint32_t diff = tr_key_spread(o, a, s_w, lane, wave);      // (its barrier also orders the key stores and the counts)
+    if (diff == 0u) return;
+    uint32_t *sk = ak, *sv = pl, *dk = bk, *dv = bv;
+#pragma unroll 1
+    for (int p = 0; p < RS_MAX_PASSES; p++) {
+        const int shift = p * RS_BITS;
+        if (((diff >> shift) & (RS_RADIX - 1u)) == 0u) continue;
+        s_base[tid] = tr_digit_scan(s_hist[p][tid], s_w + 2 * TR_WAVES, lane, wave);      // first slot of digit tid
+        __syncthreads();
+        for (uint32_t c0 = 0; c0 < n; c0 += (uint32_t)(RS_THREADS * TR_CHUNK_IPT)) {
+            const uint32_t wbase = c0 + (uint32_t)wave * (64u * TR_CHUNK_IPT);
+            uint32_t k[TR_CHUNK_IPT], v[TR_CHUNK_IPT], rank[TR_CHUNK_IPT];
+#pragma unroll
+            for (int it = 0; it < TR_CHUNK_IPT; it++) {
+                const uint32_t idx = wbase + (uint32_t)it * 64u + lane;
+                k[it] = idx < n ? sk[idx] : 0xffffffffu;
+                v[it] = idx < n ? sv[idx] : 0u;
+            }
+#pragma unroll
+            for (int it = 0; it < TR_CHUNK_IPT; it++) {
+                rank[it] = tr_rank((k[it] >> shift) & (RS_RADIX - 1u), wbase + (uint32_t)it * 64u + lane < n, s_cnt[wave]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();
+            uint32_t run = s_base[tid];      // thread = digit: the chunk's waves take their slots in wave order
+#pragma unroll
+            for (int w = 0; w < TR_WAVES; w++) { const uint32_t c = s_cnt[w][tid]; s_cnt[w][tid] = run; run += c; }
+            s_base[tid] = run;
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < TR_CHUNK_IPT; it++) {
+                if (wbase + (uint32_t)it * 64u + lane < n) {
+                    const uint32_t dst = s_cnt[wave][(k[it] >> shift) & (RS_RADIX - 1u)] + rank[it];      // a slot of this run
+                    if (dst < n) { dk[dst] = k[it]; dv[dst] = v[it]; }      // (always: the digit totals count these very keys)
+                }
+            }
+            for (int j = lane; j < RS_RADIX; j += 64) s_cnt[wave][j] = 0u;
+        }
+        __syncthreads();      // the pass's stores, in front of the next pass's loads (one workgroup: one CU, one vector cache)
+        uint32_t* t = sk; sk = dk; dk = t;
+        t = sv; sv = dv; dv = t;
+    }
+    if (sv != pl) for (uint32_t i = tid; i < n; i += RS_THREADS) pl[i] = sv[i];
+}
+
+// TS_CAP = largest run sorted inside LDS (8 B per item + 4 KB of digit counters).  LDS is granted in pieces of 1 280 B out of 160 KB
+// per CU: 1536 -> 16 KB + 48 B -> 13 pieces, 9 workgroups (more than the 8 that 32 waves allow) for frames whose tiles are small;
+// 4096 -> 36 KB + 48 B -> 29 pieces, 4 workgroups otherwise.  The network (runs <= radix_min <= 2048) uses the same bytes.
 template <int TS_CAP>
 __global__ void __launch_bounds__(RS_THREADS) tile_depth_sort_kernel(uint2* __restrict__ ranges, uint32_t* __restrict__ point_list,
                                                                     const uint32_t* __restrict__ depth_keys, uint32_t* __restrict__ tmp_ids,
-                                                                    uint32_t* __restrict__ tmp_keys, uint32_t* __restrict__ tmp_rank, int decode) {
-    __shared__ unsigned long long s[TS_CAP];       // 32 KB: (depth bits << 32) | surfel index
+                                                                    uint32_t* __restrict__ tmp_keys, uint32_t* __restrict__ tmp_rank, int decode,
+                                                                    uint32_t radix_min) {
+    static_assert(TS_CAP % RS_THREADS == 0 && TS_CAP * 8 + 4 * TR_WAVES * RS_RADIX >= TR_BITONIC_MAX * 8, "LDS layout");
+    __shared__ unsigned long long s_raw[TS_CAP + TR_WAVES * RS_RADIX / 2];
+    __shared__ uint32_t s_w[3 * TR_WAVES];
+    unsigned long long* s = s_raw;                                                  // network: (depth bits << 32) | surfel index
+    uint32_t (*s_cnt)[RS_RADIX] = reinterpret_cast<uint32_t (*)[RS_RADIX]>(s_raw);  // radix: 4 KB of per-wave digit counters ...
+    uint2* s_item = reinterpret_cast<uint2*>(s_raw + TR_WAVES * RS_RADIX / 2);      // ... and TS_CAP (key, id) items behind them
     uint2 rg = ranges[blockIdx.x];
     if (decode) {      // ranges left by the sort's last pass (os_pass_fat_kernel): the start is stored complemented
         // every wave must HOLD the undecoded word before thread 0 overwrites it (a wave whose load landed after the store would complement
@@ -501,42 +686,45 @@ __global__ void __launch_bounds__(RS_THREADS) tile_depth_sort_kernel(uint2* __re
     if (n < 2u) return;
     uint32_t* __restrict__ pl = point_list + rg.x;
     const uint32_t tid = threadIdx.x;
-    // up to TS_CAP instances: E elements per thread, the network runs in registers (see tile_sort_regs)
-    if (n <= (uint32_t)RS_THREADS) { tile_sort_regs<1>(n, pl, depth_keys, s, tid); return; }
-    if (n <= 2u * RS_THREADS) { tile_sort_regs<2>(n, pl, depth_keys, s, tid); return; }
-    if (n <= 4u * RS_THREADS) { tile_sort_regs<4>(n, pl, depth_keys, s, tid); return; }
-    if (n <= 8u * RS_THREADS) { tile_sort_regs<8>(n, pl, depth_keys, s, tid); return; }
-    if (TS_CAP >= 16 * RS_THREADS && n <= 16u * RS_THREADS) { tile_sort_regs<(TS_CAP >= 16 * RS_THREADS ? 16 : 8)>(n, pl, depth_keys, s, tid); return; }
-    // fallback: rank of element i = number of elements with a smaller (depth, index) key; chunks of TS_CAP keys through LDS
-    uint32_t* __restrict__ ids = tmp_ids + rg.x;
-    uint32_t* __restrict__ keys = tmp_keys + rg.x;
-    uint32_t* __restrict__ rank = tmp_rank + rg.x;
-    for (uint32_t i = tid; i < n; i += RS_THREADS) { const uint32_t id = pl[i]; ids[i] = id; keys[i] = depth_keys[id]; rank[i] = 0u; }
-    __syncthreads();
-    for (uint32_t c0 = 0; c0 < n; c0 += (uint32_t)TS_CAP) {
-        const uint32_t m = min((uint32_t)TS_CAP, n - c0);
-        for (uint32_t i = tid; i < m; i += RS_THREADS) s[i] = ((unsigned long long)keys[c0 + i] << 32) | ids[c0 + i];
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += RS_THREADS) {
-            const unsigned long long mine = ((unsigned long long)keys[i] << 32) | ids[i];
-            uint32_t r = 0;
-            for (uint32_t j = 0; j < m; j++) r += s[j] < mine ? 1u : 0u;
-            rank[i] += r;
-        }
-        __syncthreads();
+    // short runs (radix_min <= TR_BITONIC_MAX): E elements per thread, the network runs in registers (see tile_sort_regs)
+    if (n <= radix_min) {
+        if (n <= (uint32_t)RS_THREADS) { tile_sort_regs<1>(n, pl, depth_keys, s, tid); return; }
+        if (n <= 2u * RS_THREADS) { tile_sort_regs<2>(n, pl, depth_keys, s, tid); return; }
+        if (n <= 4u * RS_THREADS) { tile_sort_regs<4>(n, pl, depth_keys, s, tid); return; }
+        tile_sort_regs<8>(n, pl, depth_keys, s, tid);
+        return;
     }
-    for (uint32_t i = tid; i < n; i += RS_THREADS) pl[rank[i]] = ids[i];
+    // up to TS_CAP: radix passes inside LDS, the items in registers between them
+    if (n <= 4u * RS_THREADS) { tile_radix_lds<4>(n, pl, depth_keys, s_cnt, s_item, s_w, tid); return; }
+    constexpr int MID = TS_CAP < 8 * RS_THREADS ? TS_CAP : 8 * RS_THREADS;
+    if (n <= (uint32_t)MID) { tile_radix_lds<MID / RS_THREADS>(n, pl, depth_keys, s_cnt, s_item, s_w, tid); return; }
+    if constexpr (TS_CAP > MID) {
+        if (n <= (uint32_t)TS_CAP) { tile_radix_lds<TS_CAP / RS_THREADS>(n, pl, depth_keys, s_cnt, s_item, s_w, tid); return; }
+    }
+    // beyond: the same passes, chunked through the tile's slices of the sort's ping-pong buffers (digit totals and slots where the items were)
+    tile_radix_chunked(n, pl, depth_keys, tmp_keys + rg.x, tmp_rank + rg.x, tmp_ids + rg.x, s_cnt, reinterpret_cast<uint32_t (*)[RS_RADIX]>(s_item),
+                       reinterpret_cast<uint32_t*>(s_item) + RS_MAX_PASSES * RS_RADIX, s_w, tid);
+}
+
+constexpr int TS_CAP_SMALL = 1536, TS_CAP_LARGE = 4096;
+constexpr int TS_SMALL_MAX_AVG = 256;      // frames with at most this many instances per tile take the small-LDS kernel
+// what a caller (and the tests) need to know about the size classes: [0] longest run of the register network, [1] / [2] LDS capacity of
+// the small / large kernel, [3] instances per tile up to which a frame takes the small kernel, [4] / [5] register classes of the LDS radix
+int tile_depth_sort_classes(int* out, int cap) {
+    const int v[6] = {g_tile_radix_min, TS_CAP_SMALL, TS_CAP_LARGE, TS_SMALL_MAX_AVG, 4 * RS_THREADS, 8 * RS_THREADS};
+    for (int i = 0; i < 6 && i < cap; i++) out[i] = v[i];
+    return 6;
 }
 
 void launch_tile_depth_sort(int ntiles, int64_t R, uint2* ranges, uint32_t* point_list, const uint32_t* depth_keys, uint32_t* tmp_ids,
                             uint32_t* tmp_keys, uint32_t* tmp_rank, bool decode, hipStream_t st) {
     if (ntiles <= 0) return;
-    if (R <= (int64_t)256 * ntiles)
-        hipLaunchKernelGGL(tile_depth_sort_kernel<2048>, dim3(ntiles), dim3(RS_THREADS), 0, st, ranges, point_list, depth_keys, tmp_ids, tmp_keys,
-                           tmp_rank, decode ? 1 : 0);
+    if (R <= (int64_t)TS_SMALL_MAX_AVG * ntiles)
+        hipLaunchKernelGGL(tile_depth_sort_kernel<TS_CAP_SMALL>, dim3(ntiles), dim3(RS_THREADS), 0, st, ranges, point_list, depth_keys, tmp_ids,
+                           tmp_keys, tmp_rank, decode ? 1 : 0, (uint32_t)g_tile_radix_min);
     else
-        hipLaunchKernelGGL(tile_depth_sort_kernel<4096>, dim3(ntiles), dim3(RS_THREADS), 0, st, ranges, point_list, depth_keys, tmp_ids, tmp_keys,
-                           tmp_rank, decode ? 1 : 0);
+        hipLaunchKernelGGL(tile_depth_sort_kernel<TS_CAP_LARGE>, dim3(ntiles), dim3(RS_THREADS), 0, st, ranges, point_list, depth_keys, tmp_ids,
+                           tmp_keys, tmp_rank, decode ? 1 : 0, (uint32_t)g_tile_radix_min);
 }
 
 // Sorts on key bits [begin_bit, end_bit).  Buffers ping-pong a -> b -> a ...; returns 0 if the result is in (keys_a, vals_a),

@@ -98,6 +98,9 @@ SIGNATURES = {
         "surfel_collect_stage_ms": (_i, _fp, _ip, _i),
         "surfel_stage_name": (C.c_char_p, _i),
         "surfel_debug_sort_pairs": (_i, _a, _u, _d, _d, _i64, _i, _i, _s),
+        "surfel_debug_tile_depth_sort": (_i, _i, _i64, _d, _d, _d, _d, _i, _s),
+        "surfel_debug_tile_depth_sort_classes": (_i, _ip, _i),
+        "surfel_debug_set_tile_radix_min": (_i, _i),
         "surfel_debug_set_blend_stats": (_i, _d),
         "surfel_debug_last_binning": (_i,),
         "surfel_debug_capacity_evictions": (_i,),

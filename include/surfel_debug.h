@@ -23,6 +23,19 @@ const char* surfel_stage_name(int stage);
 int surfel_debug_sort_pairs(surfel_alloc_fn scratch_alloc, void* scratch_user, uint32_t* keys, uint32_t* vals, int64_t n,
                             int begin_bit, int end_bit, void* stream);
 
+/* The per-tile depth sort on its own: run t = point_list[ranges[2 t], ranges[2 t + 1]) (surfel ids, ASCENDING inside every run; runs
+ * disjoint, inside [0, n)) comes out ordered by (depth_keys[id], id); nothing outside the runs is touched.  decode != 0: ranges as the
+ * capacity path's tile sort leaves them (start complemented, (0, 0) = empty tile), written back decoded.  scratch: 3 n words.  n also
+ * picks the kernel as a frame's instance count does (n / ntiles). */
+int surfel_debug_tile_depth_sort(int ntiles, int64_t n, uint32_t* ranges, uint32_t* point_list, const uint32_t* depth_keys, uint32_t* scratch,
+                                 int decode, void* stream);
+/* Its size classes (HOST pointer, cap >= 6): out[0] longest run of the register network, [1] / [2] longest run sorted inside LDS by the
+ * small / large kernel (longer ones are streamed in chunks), [3] n / ntiles up to which the small kernel is taken, [4] / [5] run lengths
+ * at which the LDS radix changes its register class.  Returns the number of values. */
+int surfel_debug_tile_depth_sort_classes(int* out, int cap);
+/* Measurement only: the longest run the register network takes (0 ... 2048; < 0 restores the default). */
+int surfel_debug_set_tile_radix_min(int longest_network_run);
+
 /* A device buffer of 8 uint64 (caller-zeroed) that every following blend-backward launch accumulates into — [0] lane slots issued,
  * [1] lanes that held a composited pair, [2] wave visits, [3] (sub-tile | quad, instance) visits, [4] of those with a composited pair,
  * [5] quad variant: 4x4 sub-tiles with a composited pair — or NULL to switch the instrumented kernels off. */
