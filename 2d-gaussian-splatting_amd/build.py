@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsurfel_hip.so")
 SOURCES = ["surfel_preprocess.hip", "surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_sort.hip", "surfel_api.hip", "knn.hip", "box_probe.hip",
            "train_loss.hip", "train_post.hip", "train_fused.hip", "train_optim.hip", "train_api.hip",
-           "device_scan.hip", "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "mesh_view.hip", "frame_jpeg.hip", "frame_png.hip", "scene_jpeg.hip", "scene_undistort.hip", "train_log.hip", "log_events.cpp", "mesh_simplify.hip", "mesh_texture.hip", "mesh_smooth.hip"]
+           "device_scan.hip", "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "mesh_view.hip", "frame_jpeg.hip", "frame_png.hip", "scene_jpeg.hip", "scene_undistort.hip", "train_log.hip", "log_events.cpp", "mesh_simplify.hip", "mesh_texture.hip", "mesh_smooth.hip", "mesh_repair.hip"]
 # blend kernels: packed-f32 VALU (SLP) costs ~1.6x a scalar op on gfx950 plus the v_movs that pair the operands
 # surfel_backward.hip spells every fused multiply-add out (FMA macro) and is compiled with contraction off, so its kernel variants
 # round identically per (pixel, surfel) pair
@@ -56,7 +56,10 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          "mesh_texture.hip": ["-ffp-contract=off"],
          # mesh_smooth.hip: no contraction, so a filter step's fp64 mean and blend (a product, then a sum) round as their restatement
          # (tests/smooth_oracle.py) and the smoothed vertices come out bit for bit
-         "mesh_smooth.hip": ["-ffp-contract=off"]}
+         "mesh_smooth.hip": ["-ffp-contract=off"],
+         # mesh_repair.hip: no contraction, so a fill centroid's fp64 sum and division round as their restatement
+         # (tests/repair_oracle.py) and the repaired vertices come out bit for bit
+         "mesh_repair.hip": ["-ffp-contract=off"]}
 HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
            os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", "mesh_mc.h", "block_ops.h", "side_util.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
            os.path.join("..", "..", "include", "surfel_mesh_unbounded.h"), os.path.join("..", "..", "include", "surfel_eval.h"),
@@ -67,7 +70,8 @@ HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_blend_bwd.h", "train_k
            os.path.join("..", "..", "include", "surfel_jpegdec.h"), os.path.join("..", "..", "include", "surfel_undistort.h"),
            "log_jet_table.h", os.path.join("..", "..", "include", "surfel_log.h"), "mesh_raster.h", "mesh_sample.h",
            os.path.join("..", "..", "include", "surfel_meshview.h"), os.path.join("..", "..", "include", "surfel_simplify.h"),
-           os.path.join("..", "..", "include", "surfel_texture.h"), os.path.join("..", "..", "include", "surfel_smooth.h")]
+           os.path.join("..", "..", "include", "surfel_texture.h"), os.path.join("..", "..", "include", "surfel_smooth.h"),
+           os.path.join("..", "..", "include", "surfel_repair.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-result"]
 
 

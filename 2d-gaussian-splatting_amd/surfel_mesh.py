@@ -492,6 +492,10 @@ def build_parser():
     ap.add_argument("--smooth_method", default="taubin", choices=["taubin", "laplacian"], help="Mesh: the filter of --smooth_iterations")
     ap.add_argument("--smooth_boundary", default="free", choices=["free", "fixed", "curve"], help="Mesh: what --smooth_iterations does at the "
                     "mesh's border: every neighbour counts, boundary vertices stay, or they average along the border only")
+    ap.add_argument("--repair", action="store_true", help="Mesh: also write fuse_post_repaired.ply (fuse_unbounded_post_repaired.ply), the "
+                    "post-processed mesh with its non-manifold edges cut, its vertices split into one fan each and its small holes closed "
+                    "(REPAIR.md); --smooth_iterations, --simplify_*, --texture and --render_mesh then continue from it")
+    ap.add_argument("--repair_max_hole", default=32, type=int, help="Mesh: --repair closes the border loops of at most this many edges")
     return ap
 
 
@@ -515,6 +519,8 @@ def main(argv=None):
         raise SystemExit("--simplify_cell must be positive")
     if args.smooth_iterations is not None and args.smooth_iterations < 0:
         raise SystemExit("--smooth_iterations must not be negative")
+    if args.repair_max_hole < 0:
+        raise SystemExit("--repair_max_hole must not be negative")
     import surfel_io
     import surfel_model
     from surfel_render import render
@@ -574,6 +580,12 @@ def main(argv=None):
     post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
     surfel_io.write_triangle_mesh(os.path.join(out, name.replace(".ply", "_post.ply")), post)
     print("mesh post processed saved at {}".format(os.path.join(out, name.replace(".ply", "_post.ply"))))
+    if args.repair:      # before the filter, which then evens out the fill fans; the steps below continue from the repaired mesh
+        import surfel_repair
+        post, stats = surfel_repair.repair_mesh(post, max_hole_edges=args.repair_max_hole)
+        repair_path = os.path.join(out, name.replace(".ply", "_post_repaired.ply"))
+        surfel_io.write_triangle_mesh(repair_path, post)
+        print("mesh repaired ({}) saved at {}".format(surfel_repair.summary(stats), repair_path))
     if args.smooth_iterations is not None:      # the steps below continue from the smoothed mesh
         import surfel_smooth
         post, stats = surfel_smooth.smooth_mesh(post, iterations=args.smooth_iterations, method=args.smooth_method, boundary=args.smooth_boundary)

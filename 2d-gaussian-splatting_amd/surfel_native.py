@@ -72,11 +72,19 @@ class JpegDecDesc(C.Structure):
                 ("bits", (C.c_uint8 * 16) * 4), ("huffval", (C.c_uint8 * 256) * 4)]
 
 
-# ---- every exported function: name -> (restype, parameter types ...), grouped by the header that declares it.  d = device pointer,
+class RepairPlan(C.Structure):
+    """surfel_repair_plan of include/surfel_repair.h (a host structure; its arrays are device memory from the caller's allocator)"""
+    _fields_ = [(k, C.c_int64) for k in ("V", "F", "max_hole_edges", "survivors", "split", "border", "loops", "fill_triangles", "fill_vertices")] + \
+               [(k, C.c_void_p) for k in ("triangles", "triangle_source", "split_source", "half_edge", "loop", "position", "lengths", "fill_vertex",
+                                          "fill_offset", "triangle_offset", "centroid_offset")]
+
+
+# ---- every exported function: name ->(restype, parameter types ...), grouped by the header that declares it.  d = device pointer,
 # s = the stream, u = any other void*, a = allocator callback; host pointers keep their POINTER(...) type.
 _i, _i64, _f, _f64, _d, _s, _u, _a = C.c_int, C.c_int64, C.c_float, C.c_double, DevPtr, Stream, C.c_void_p, ALLOC_FN
 _fp, _ip, _i64p, _f64p = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _vol, _uvol, _grid, _jdesc = C.POINTER(TsdfVolume), C.POINTER(UnboundedVolume), C.POINTER(EvalGrid), C.POINTER(JpegDecDesc)
+_rplan = C.POINTER(RepairPlan)
 _adam = (_i, _d, _d, _d, _d, _d, _fp, _f, _f, _f, _i, _f, _i, _i, _d, _d)      # surfel_adam_step up to gcol_all
 SIGNATURES = {
     "surfel_hip.h": {
@@ -216,6 +224,11 @@ SIGNATURES = {
         "surfel_smooth_adjacency": (_i64, _a, _u, _i64, _i64, _d, _d, _d, _d, _d, _d, _i64p, _s),      # counts, factors: HOST pointers
         "surfel_smooth_steps": (_i, _i64, _d, _d, _d, _d, _i, _i, _f64p, _d, _d, _d, _s),
     },
+    "surfel_repair.h": {
+        "surfel_repair_analyze": (_i, _a, _u, _i64, _i64, _d, _d, _i64, _rplan, _i64p, _fp, _s),      # plan, counts, stage_ms: HOST pointers
+        "surfel_repair_emit": (_i, _rplan, _d, _d, _d, _d, _d, _d, _d, _d, _s),
+        "surfel_repair_loops": (_i, _rplan, _d, _d, _d, _d, _s),
+    },
     "surfel_jpeg.h": {
         "surfel_jpeg_capacity": (_i64, _i, _i),
         "surfel_jpeg_scratch_bytes": (_i64, _i, _i),
@@ -256,6 +269,7 @@ MESHVIEW_EXPORTS = list(SIGNATURES["surfel_meshview.h"])
 SIMPLIFY_EXPORTS = list(SIGNATURES["surfel_simplify.h"])
 TEXTURE_EXPORTS = list(SIGNATURES["surfel_texture.h"])
 SMOOTH_EXPORTS = list(SIGNATURES["surfel_smooth.h"])
+REPAIR_EXPORTS = list(SIGNATURES["surfel_repair.h"])
 JPEG_EXPORTS = list(SIGNATURES["surfel_jpeg.h"])
 PNG_EXPORTS = list(SIGNATURES["surfel_png.h"])
 JPEGDEC_EXPORTS = list(SIGNATURES["surfel_jpegdec.h"])
