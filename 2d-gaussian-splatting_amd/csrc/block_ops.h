@@ -1,10 +1,22 @@
-// block_ops.h — scans and reductions over a workgroup of NT threads (a multiple of 64), device only.  Every thread of the workgroup
-// calls them together.  s_w: NT / 64 words of LDS; each function opens with a barrier, so s_w may be reused from call to call.
+// block_ops.h — sums and extrema over the 64 lanes of a wave, and scans and reductions over a workgroup of NT threads (a multiple of
+// 64), device only.  Every thread of the wave / workgroup calls them together.  s_w: NT / 64 words of LDS; each workgroup function opens
+// with a barrier, so s_w may be reused from call to call.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace surfel {
+
+// xor-shuffle reductions over the 64 lanes of a wave: every lane returns the result
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a + b; }); }
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return max(a, b); }); }
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return min(a, b); }); }
 
 __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {      // inclusive scan over the 64 lanes of a wave
     const int lane = threadIdx.x & 63;
@@ -72,8 +84,7 @@ __device__ __forceinline__ uint32_t block_scan_min_suffix(uint32_t v, uint32_t* 
 template <int NT>
 __device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t* s_w) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor(v, off, 64));
+    v = wave_min(v);
     __syncthreads();
     if (lane == 0) s_w[wv] = v;
     __syncthreads();
@@ -86,8 +97,7 @@ __device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t* s_w) {
 template <int NT>
 __device__ __forceinline__ uint64_t block_sum64(uint64_t v, uint64_t* s_w) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
+    v = wave_reduce(v, [](uint64_t a, uint64_t b) { return a + b; });
     __syncthreads();
     if (lane == 0) s_w[wv] = v;
     __syncthreads();
@@ -100,8 +110,7 @@ __device__ __forceinline__ uint64_t block_sum64(uint64_t v, uint64_t* s_w) {
 template <int NT>
 __device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t* s_w) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v ^= (uint32_t)__shfl_xor(v, off, 64);
+    v = wave_reduce(v, [](uint32_t a, uint32_t b) { return a ^ b; });
     __syncthreads();
     if (lane == 0) s_w[wv] = v;
     __syncthreads();

@@ -95,15 +95,14 @@ __global__ void __launch_bounds__(TT) tnt_voxel_keys_kernel(int64_t n, const flo
         key = (uint64_t)cx | (uint64_t)cy << AXIS_BITS | (uint64_t)cz << (2 * AXIS_BITS);
     else
         atomicOr(flags, 1u);
-    lo[i] = (uint32_t)key; hi[i] = (uint32_t)(key >> 32);
-    ka[i] = (uint32_t)key; va[i] = (uint32_t)i;
+    lo[i] = key_word(key, 0); hi[i] = key_word(key, 1);
+    ka[i] = key_word(key, 0); va[i] = (uint32_t)i;      // (VoxelKey's word 0, from the register)
 }
 
-__global__ void __launch_bounds__(TT) tnt_voxel_hi_kernel(int64_t n, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ val,
-                                                          uint32_t* __restrict__ key) {
-    const int64_t j = (int64_t)blockIdx.x * TT + threadIdx.x;
-    if (j < n) key[j] = hi[val[j]];
-}
+struct VoxelKey {      // the sort's key of a point: the two words of its cell key
+    const uint32_t *lo, *hi;
+    __device__ uint32_t operator()(uint32_t i, int word) const { return word ? hi[i] : lo[i]; }
+};
 
 __device__ inline uint64_t tnt_key_of(const uint32_t* lo, const uint32_t* hi, uint32_t i) { return (uint64_t)hi[i] << 32 | lo[i]; }
 
@@ -263,10 +262,8 @@ int64_t surfel_tnt_voxel_down_sample(surfel_alloc_fn alloc, void* user, int64_t 
     if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return api_fail(SURFEL_E_HIP, "tnt_voxel_down_sample: memset", hipGetLastError());
     const TVox v{origin[0], origin[1], origin[2], voxel};
     hipLaunchKernelGGL(tnt_voxel_keys_kernel, dim3(grid(n)), dim3(TT), 0, st, n, points, v, lo, hi, s.ka, s.va, flag);
-    // the 63-bit key as two stable LSD sorts of its 32-bit halves: low word first, then high word
-    if (s.sort(32, st) < 0) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
-    hipLaunchKernelGGL(tnt_voxel_hi_kernel, dim3(grid(n)), dim3(TT), 0, st, n, hi, s.va, s.ka);
-    if (s.sort(3 * AXIS_BITS - 32, st) < 0) return api_fail(SURFEL_E_LIMIT, "tnt_voxel_down_sample: sort");
+    const int bits[2] = {32, 3 * AXIS_BITS - 32};      // the 63-bit key by its 32-bit words
+    if (int rc = sort_words(s, VoxelKey{lo, hi}, 2, bits, "tnt_voxel_down_sample: sort", st)) return rc;
     const uint32_t* perm = s.va;
     hipLaunchKernelGGL(tnt_voxel_heads_kernel, dim3(grid(n + 1)), dim3(TT), 0, st, n, lo, hi, perm, head.flags);
     head.scan(st);

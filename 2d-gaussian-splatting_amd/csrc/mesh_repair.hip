@@ -1,5 +1,5 @@
-// mesh_repair.hip — manifold cut, fan split and hole fill of a triangle mesh (include/surfel_repair.h, REPAIR.md): kept triangles -> three
-// half-edges each -> the library's stable two-word sort by (min, max) of the ends, so that a run is an undirected edge -> a lane per
+// mesh_repair.hip — manifold cut, fan split and hole fill of a triangle mesh (include/surfel_repair.h, REPAIR.md): kept triangles (mesh_topology.h) -> three
+// half-edges each -> sort_words (side_util.h) by (min, max) of the ends, so that a run is an undirected edge -> a lane per
 // sorted slot looks two slots to either side: the run's length and directions decide the cut, a run of two is a pair of twins -> fans and
 // border loops are orbits of a successor array, labelled and ranked by pointer jumping, one launch per round (orbit_round_kernel) -> the
 // extra fans of a vertex are ranked by one sort of (vertex, label) -> filled loops are scattered to offset[loop] + position, a workgroup
@@ -11,7 +11,8 @@
 #include <math.h>
 
 #include "../../include/surfel_repair.h"
-#include "side_util.h"
+#include "block_ops.h"
+#include "mesh_topology.h"
 
 namespace surfel {
 
@@ -21,71 +22,34 @@ constexpr uint32_t HEAD_BIT = 0x80000000u;               // a fan's key: the hea
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 enum { T_NONMANIFOLD, T_MISORIENTED, T_LONGEST, T_FILLED, T_FILL_TRIS, T_FILL_VERTS, T_FILL_EDGES, T_WORDS };
 
-// after an exclusive scan of flags: was element i flagged
-__device__ __forceinline__ bool scanned_flag(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ total, int64_t i, int64_t n) {
-    return (i + 1 < n ? pos[i + 1] : *total) != pos[i];
-}
-
 // the ends of half-edge 3 t + k of the input: lo < hi, fwd when it runs lo -> hi
 __device__ __forceinline__ void repair_edge(const int32_t* __restrict__ tris, uint32_t h, uint32_t* lo, uint32_t* hi, bool* fwd) {
-    const uint32_t t = h / 3u, k = h - 3u * t, k1 = k == 2u ? 0u : k + 1u;
-    const uint32_t a = (uint32_t)tris[3 * (int64_t)t + k], b = (uint32_t)tris[3 * (int64_t)t + k1];
+    uint32_t a, b;
+    half_edge_ends(tris, h, &a, &b);
     *lo = min(a, b); *hi = max(a, b); *fwd = a < b;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-    return v;
-}
-
-// ---- rules 1-3: kept triangles, the sort's keys, the cut -------------------------------------------------------------------------------
-// keep[t] = 1 for a triangle of three distinct indices in [0, V) whose vertices are finite (rule 1, SMOOTH.md's)
-__global__ void __launch_bounds__(RT) repair_keep_kernel(int64_t F, int64_t V, const float* __restrict__ verts, const int32_t* __restrict__ tris,
-                                                         uint32_t* __restrict__ keep) {
-    const int64_t t = (int64_t)blockIdx.x * RT + threadIdx.x;
-    if (t >= F) return;
-    const int32_t idx[3] = {tris[3 * t], tris[3 * t + 1], tris[3 * t + 2]};
-    bool ok = idx[0] != idx[1] && idx[1] != idx[2] && idx[0] != idx[2];
-#pragma unroll
-    for (int k = 0; k < 3; k++) ok = ok && idx[k] >= 0 && idx[k] < V;
-    if (ok) {
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            ok = ok && __builtin_isfinite(verts[3 * (int64_t)idx[k]]) && __builtin_isfinite(verts[3 * (int64_t)idx[k] + 1]) &&
-                 __builtin_isfinite(verts[3 * (int64_t)idx[k] + 2]);
+struct RepairKey {      // the sort's key (lo, hi) of a half-edge: word 0 = hi, word 1 = lo
+    const int32_t* tris;
+    __device__ uint32_t operator()(uint32_t h, int word) const {
+        uint32_t lo, hi; bool fwd;
+        repair_edge(tris, h, &lo, &hi, &fwd);
+        return word ? lo : hi;
     }
-    keep[t] = ok ? 1u : 0u;
-}
+};
 
+// ---- rules 1-3: kept triangles (mesh_topology.h), the sort's keys, the cut ---------------------------------------------------------------
 // after the scan of keep: the three half-edges of kept triangle number m at 3 m ..: key = the larger end, value = 3 t + k
-__global__ void __launch_bounds__(RT) repair_emit_kernel(int64_t F, const int32_t* __restrict__ tris, const uint32_t* __restrict__ pos,
+__global__ void __launch_bounds__(RT) repair_emit_kernel(int64_t F, RepairKey key_of, const uint32_t* __restrict__ pos,
                                                          const uint32_t* __restrict__ total, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     const int64_t t = (int64_t)blockIdx.x * RT + threadIdx.x;
     if (t >= F || !scanned_flag(pos, total, t, F)) return;
     const int64_t m = pos[t];
 #pragma unroll
     for (uint32_t k = 0; k < 3; k++) {
-        uint32_t lo, hi; bool fwd;
-        repair_edge(tris, 3u * (uint32_t)t + k, &lo, &hi, &fwd);
-        key[3 * m + k] = hi;
+        key[3 * m + k] = key_of(3u * (uint32_t)t + k, 0);
         val[3 * m + k] = 3u * (uint32_t)t + k;
     }
-}
-
-__global__ void __launch_bounds__(RT) repair_key_lo_kernel(int64_t n, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val,
-                                                           uint32_t* __restrict__ key) {
-    const int64_t j = (int64_t)blockIdx.x * RT + threadIdx.x;
-    if (j >= n) return;
-    uint32_t lo, hi; bool fwd;
-    repair_edge(tris, val[j], &lo, &hi, &fwd);
-    key[j] = lo;
 }
 
 // Rule 3 on the sorted half-edges.  Slot j sees the slots up to two away: its run has more than two members iff three neighbouring slots
@@ -472,14 +436,7 @@ int surfel_repair_analyze(surfel_alloc_fn alloc, void* user, int64_t V, int64_t 
     if (hipMemsetAsync(dtally, 0, sizeof(tally), st) != hipSuccess) return api_fail(SURFEL_E_HIP, what, hipGetLastError());
     // ---- the sort
     ScanBuf keep;
-    if (F > 0 && V > 0) {
-        keep = take_scan(alloc, user, F);
-        if (!keep.flags) return api_fail(SURFEL_E_ALLOC, what);
-        hipLaunchKernelGGL(repair_keep_kernel, dim3(grid(F)), dim3(RT), 0, st, F, V, verts, tris, keep.flags);
-        keep.scan(st);
-        if (int rc = read_words(what, keep.total, &kept, 1, st)) return rc;      // (the sort is sized by the kept triangles)
-        if (int rc = launched("repair_keep_kernel")) return rc;
-    }
+    if (int rc = mesh_keep(what, alloc, user, V, F, verts, tris, &keep, &kept, st)) return rc;
     const int64_t n = 3 * (int64_t)kept;
     if (kept > 0) {
         SortPairs s(alloc, user, n);
@@ -487,11 +444,10 @@ int surfel_repair_analyze(surfel_alloc_fn alloc, void* user, int64_t V, int64_t 
         uint32_t* cut = take<uint32_t>(alloc, user, F);
         uint32_t* partner = take<uint32_t>(alloc, user, n);
         if (!s.ok() || !surv.flags || !cut || !partner) return api_fail(SURFEL_E_ALLOC, what);
-        hipLaunchKernelGGL(repair_emit_kernel, dim3(grid(F)), dim3(RT), 0, st, F, tris, keep.flags, keep.total, s.ka, s.va);
-        // (lo, hi) as two stable LSD sorts: the low word hi, then the high word lo, bit_length(V - 1) bits each
-        if (s.sort(bit_length(V - 1), st) < 0) return api_fail(SURFEL_E_LIMIT, "repair_analyze: sort");
-        hipLaunchKernelGGL(repair_key_lo_kernel, dim3(grid(n)), dim3(RT), 0, st, n, tris, s.va, s.ka);
-        if (s.sort(bit_length(V - 1), st) < 0) return api_fail(SURFEL_E_LIMIT, "repair_analyze: sort");
+        const RepairKey key_of{tris};
+        const int bits[2] = {bit_length(V - 1), bit_length(V - 1)};
+        hipLaunchKernelGGL(repair_emit_kernel, dim3(grid(F)), dim3(RT), 0, st, F, key_of, keep.flags, keep.total, s.ka, s.va);
+        if (int rc = sort_words(s, key_of, 2, bits, "repair_analyze: sort", st)) return rc;
         stages.mark();
         // ---- the cut, the survivors, the twins
         if (hipMemsetAsync(cut, 0, (size_t)F * 4, st) != hipSuccess) return api_fail(SURFEL_E_HIP, what, hipGetLastError());

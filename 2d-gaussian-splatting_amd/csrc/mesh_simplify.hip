@@ -1,6 +1,6 @@
 // mesh_simplify.hip — mesh simplification by quadric vertex clustering (include/surfel_simplify.h, SIMPLIFY.md): vertices -> 63-bit cell
-// keys -> the library's stable sort -> run heads and a scan number the occupied cells; triangles mapped through the cells, those that
-// repeat a cell dropped, later copies of a rotated triple dropped after three stable sorts; per used cell one wave sums the plane
+// keys -> sort_words (side_util.h) -> run heads and a scan number the occupied cells; triangles mapped through the cells, those that
+// repeat a cell dropped, later copies of a rotated triple dropped after a three-word sort; per used cell one wave sums the plane
 // quadrics of the cell's (triangle, corner) incidences and its members in a fixed order in fp64 and solves the regularised 3 x 3 system
 // in closed form.
 // Compiled with -ffp-contract=off (build.py): the fp32 cell index and every fp64 operation of the sums and the solve round once, as
@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/surfel_simplify.h"
+#include "block_ops.h"
 #include "side_util.h"
 
 namespace surfel {
@@ -57,12 +58,7 @@ __global__ void __launch_bounds__(ST) simp_bounds_kernel(int64_t V, const float*
         }
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            k[c] = min(k[c], (uint32_t)__shfl_xor((int)k[c], off, 64));
-            k[c + 3] = max(k[c + 3], (uint32_t)__shfl_xor((int)k[c + 3], off, 64));
-        }
+    for (int c = 0; c < 3; c++) { k[c] = wave_min(k[c]); k[c + 3] = wave_max(k[c + 3]); }
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
         for (int c = 0; c < 6; c++) s_k[threadIdx.x >> 6][c] = k[c];
@@ -88,15 +84,14 @@ __global__ void __launch_bounds__(ST) simp_key_kernel(int64_t V, const float* __
         simp_axis(z, g.oz, g.cell, &iz))
         key = (uint64_t)iz << (2 * AXIS_BITS) | (uint64_t)iy << AXIS_BITS | ix;
     key64[i] = key;
-    key_lo[i] = (uint32_t)key;
+    key_lo[i] = key_word(key, 0);      // (CellKey's word 0, from the register)
     val[i] = (uint32_t)i;
 }
 
-__global__ void __launch_bounds__(ST) simp_key_hi_kernel(int64_t V, const uint64_t* __restrict__ key64, const uint32_t* __restrict__ val,
-                                                         uint32_t* __restrict__ key) {
-    const int64_t j = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (j < V) key[j] = (uint32_t)(key64[val[j]] >> 32);
-}
+struct CellKey {      // the sort's key of a vertex: the two words of its cell key
+    const uint64_t* key64;
+    __device__ uint32_t operator()(uint32_t v, int word) const { return key_word(key64[v], word); }
+};
 
 // head[j] = 1 where sorted slot j opens an occupied cell
 __global__ void __launch_bounds__(ST) simp_head_kernel(int64_t V, const uint64_t* __restrict__ key64, const uint32_t* __restrict__ order,
@@ -121,7 +116,7 @@ __global__ void __launch_bounds__(ST) simp_number_kernel(int64_t V, const uint64
     const uint32_t c = next - 1u;
     cluster[v] = (int32_t)c;
     if (!cstart) return;
-    if (next != excl[j]) cstart[c] = (uint32_t)j;
+    if (next != excl[j]) cstart[c] = (uint32_t)j;      // (scanned_flag, with the next entry at hand)
     if (j + 1 == V || key64[order[j + 1]] == KEY_NONE) cstart[nc] = (uint32_t)(j + 1);
 }
 
@@ -151,23 +146,21 @@ __global__ void __launch_bounds__(ST) simp_cand_kernel(int64_t F, int64_t V, con
                                                        const uint32_t* __restrict__ pos, const uint32_t* __restrict__ total, int32_t* __restrict__ trip,
                                                        uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     const int64_t t = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (t >= F) return;
-    const uint32_t m = pos[t], next = t + 1 < F ? pos[t + 1] : *total;
-    if (next == m) return;
+    if (t >= F || !scanned_flag(pos, total, t, F)) return;
+    const uint32_t m = pos[t];
     int32_t c[3];
     if (!simp_tri_cells(t, V, tris, cluster, c)) return;      // (a flagged triangle passes)
     const int r = c[0] < c[1] ? (c[0] < c[2] ? 0 : 2) : (c[1] < c[2] ? 1 : 2);
     const int32_t r0 = c[r], r1 = c[(r + 1) % 3], r2 = c[(r + 2) % 3];
     trip[3 * (int64_t)m] = r0; trip[3 * (int64_t)m + 1] = r1; trip[3 * (int64_t)m + 2] = r2;
-    key[m] = (uint32_t)r2;
+    key[m] = (uint32_t)r2;      // (TripKey's word 0, from the register)
     val[m] = m;
 }
 
-__global__ void __launch_bounds__(ST) simp_trip_key_kernel(int64_t M, const int32_t* __restrict__ trip, int word, const uint32_t* __restrict__ val,
-                                                           uint32_t* __restrict__ key) {
-    const int64_t j = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (j < M) key[j] = (uint32_t)trip[3 * (int64_t)val[j] + word];
-}
+struct TripKey {      // the sort's key of a candidate: (first, second, third cell), so word w is the triple's entry 2 - w
+    const int32_t* trip;
+    __device__ uint32_t operator()(uint32_t m, int word) const { return (uint32_t)trip[3 * (int64_t)m + 2 - word]; }
+};
 
 // keep[m] = 1 for the first candidate (lowest m: the sorts are stable) of every run of equal triples
 __global__ void __launch_bounds__(ST) simp_dup_kernel(int64_t M, const int32_t* __restrict__ trip, const uint32_t* __restrict__ order,
@@ -187,9 +180,7 @@ __global__ void __launch_bounds__(ST) simp_dup_kernel(int64_t M, const int32_t* 
 __global__ void __launch_bounds__(ST) simp_used_kernel(int64_t M, const int32_t* __restrict__ trip, const uint32_t* __restrict__ kpos,
                                                        const uint32_t* __restrict__ ktotal, uint32_t* __restrict__ used) {
     const int64_t m = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (m >= M) return;
-    const uint32_t next = m + 1 < M ? kpos[m + 1] : *ktotal;
-    if (next == kpos[m]) return;
+    if (m >= M || !scanned_flag(kpos, ktotal, m, M)) return;
     used[trip[3 * m]] = 1u; used[trip[3 * m + 1]] = 1u; used[trip[3 * m + 2]] = 1u;
 }
 
@@ -198,9 +189,8 @@ __global__ void __launch_bounds__(ST) simp_tris_out_kernel(int64_t M, const int3
                                                            const uint32_t* __restrict__ ktotal, const uint32_t* __restrict__ upos,
                                                            int32_t* __restrict__ tris_out) {
     const int64_t m = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (m >= M) return;
-    const uint32_t o = kpos[m], next = m + 1 < M ? kpos[m + 1] : *ktotal;
-    if (next == o) return;
+    if (m >= M || !scanned_flag(kpos, ktotal, m, M)) return;
+    const uint32_t o = kpos[m];
     for (int k = 0; k < 3; k++) tris_out[3 * (int64_t)o + k] = (int32_t)upos[trip[3 * m + k]];
 }
 
@@ -247,8 +237,8 @@ __global__ void __launch_bounds__(SOLVE_T) simp_solve_kernel(int64_t nc, int64_t
     __shared__ double s_sum[6 + SOLVE_TERMS];
     const int64_t c = blockIdx.x;      // (the grid has nc workgroups)
     const int lane = threadIdx.x;
-    const uint32_t o = upos[c], unext = c + 1 < nc ? upos[c + 1] : *utotal;
-    const bool used = unext != o;
+    const uint32_t o = upos[c];
+    const bool used = scanned_flag(upos, utotal, c, nc);
     if (lane == 0 && cluster_vertex) cluster_vertex[c] = used ? (int32_t)o : -1;
     if (!used) return;      // (the whole workgroup)
     const uint32_t j0 = cstart[c], j1 = cstart[c + 1];
@@ -436,10 +426,9 @@ int build_clusters(Simp& s, int32_t* cluster, bool with_starts) {
     if (!s.key64 || !sp.ok() || !head.flags) return api_fail(SURFEL_E_ALLOC, s.what);
     hipLaunchKernelGGL(simp_key_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.verts, s.g, s.key64, sp.ka, sp.va);
     if (int rc = stamp(s)) return rc;
-    // the 63-bit key as two stable LSD sorts of its 32-bit words; the key of a skipped vertex sets every bit of the high word
-    if (sp.sort(32, s.st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
-    hipLaunchKernelGGL(simp_key_hi_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, sp.va, sp.ka);
-    if (sp.sort(s.bits_hi, s.st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
+    // the 63-bit key by its 32-bit words; the key of a skipped vertex sets every bit of the high word
+    const int bits[2] = {32, s.bits_hi};
+    if (int rc = sort_words(sp, CellKey{s.key64}, 2, bits, "simplify: sort", s.st)) return rc;
     s.order = sp.va;
     hipLaunchKernelGGL(simp_head_kernel, dim3(grid(V)), dim3(ST), 0, s.st, V, s.key64, s.order, head.flags);
     head.scan(s.st);
@@ -479,11 +468,9 @@ int dedupe_triangles(Simp& s) {
     s.keep = take_scan(s.alloc, s.user, M);
     if (!s.trip || !sp.ok() || !s.keep.flags) return api_fail(SURFEL_E_ALLOC, s.what);
     hipLaunchKernelGGL(simp_cand_kernel, dim3(grid(F)), dim3(ST), 0, s.st, F, V, s.tris, s.cluster, flag.flags, flag.total, s.trip, sp.ka, sp.va);
-    // (first, second, third cell) as three stable LSD sorts: third, second, first, bit_length(nc - 1) bits each
-    for (int word = 2; word >= 0; word--) {
-        if (word < 2) hipLaunchKernelGGL(simp_trip_key_kernel, dim3(grid(M)), dim3(ST), 0, s.st, M, s.trip, word, sp.va, sp.ka);
-        if (sp.sort(bit_length(s.nc - 1), s.st) < 0) return api_fail(SURFEL_E_LIMIT, "simplify: sort");
-    }
+    // (first, second, third cell): third, second, first, bit_length(nc - 1) bits each
+    const int bits[3] = {bit_length(s.nc - 1), bit_length(s.nc - 1), bit_length(s.nc - 1)};
+    if (int rc = sort_words(sp, TripKey{s.trip}, 3, bits, "simplify: sort", s.st)) return rc;
     hipLaunchKernelGGL(simp_dup_kernel, dim3(grid(M)), dim3(ST), 0, s.st, M, s.trip, sp.va, s.keep.flags);
     s.keep.scan(s.st);
     uint32_t kept = 0;

@@ -1,5 +1,5 @@
 // mesh_smooth.hip — vertex adjacency and Laplacian / Taubin smoothing of a triangle mesh (include/surfel_smooth.h, SMOOTH.md): kept
-// triangles -> six directed vertex pairs each -> the library's stable two-word sort by (src, dst) -> run heads and a scan number the
+// triangles (mesh_topology.h) -> six directed vertex pairs each -> sort_words by (src, dst) (side_util.h) -> run heads and a scan number the
 // unique directed edges -> CSR rows by a search over the edges' sources, the run length beside every neighbour, flags and counts per
 // vertex.  A filter step is one launch: a lane per vertex gathers its row in order; a row longer than LONG_ROW is gathered by the whole
 // workgroup, a tile of ST entries at a time parked in LDS, and added in the same order.
@@ -10,7 +10,8 @@
 #include <math.h>
 
 #include "../../include/surfel_smooth.h"
-#include "side_util.h"
+#include "block_ops.h"
+#include "mesh_topology.h"
 
 namespace surfel {
 
@@ -18,55 +19,32 @@ constexpr int ST = 256;                                  // threads per workgrou
 constexpr int LONG_ROW = 32;                             // rows above this many entries are gathered by the workgroup
 constexpr int64_t SMOOTH_LIMIT = (int64_t)1 << 31;       // V and 6 F stay below
 
-// half-edge slot s = 6 t + k: edge k / 2 of triangle t runs between its corners k / 2 and (k / 2 + 1) % 3; odd k is the reversed pair
+// slot s = 2 h + r: half-edge h (mesh_topology.h), reversed when r = 1
 __device__ __forceinline__ void smooth_slot(const int32_t* __restrict__ tris, uint32_t s, uint32_t* src, uint32_t* dst) {
-    const uint32_t t = s / 6u, k = s - 6u * t, e = k >> 1, e1 = e == 2u ? 0u : e + 1u;
-    const uint32_t a = (uint32_t)tris[3 * (int64_t)t + e], b = (uint32_t)tris[3 * (int64_t)t + e1];
-    *src = (k & 1u) ? b : a;
-    *dst = (k & 1u) ? a : b;
+    if (s & 1u) half_edge_ends(tris, s >> 1, dst, src); else half_edge_ends(tris, s >> 1, src, dst);
 }
+
+struct SmoothKey {      // the sort's key (src, dst) of a slot: word 0 = dst, word 1 = src
+    const int32_t* tris;
+    __device__ uint32_t operator()(uint32_t slot, int word) const {
+        uint32_t src, dst;
+        smooth_slot(tris, slot, &src, &dst);
+        return word ? src : dst;
+    }
+};
 
 // ---- adjacency --------------------------------------------------------------------------------------------------------------------------
-// keep[t] = 1 for a triangle of three distinct indices in [0, V) whose vertices are finite (rule 1)
-__global__ void __launch_bounds__(ST) smooth_keep_kernel(int64_t F, int64_t V, const float* __restrict__ verts, const int32_t* __restrict__ tris,
-                                                         uint32_t* __restrict__ keep) {
-    const int64_t t = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (t >= F) return;
-    const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-    bool ok = a >= 0 && a < V && b >= 0 && b < V && c >= 0 && c < V && a != b && b != c && a != c;
-    if (ok) {
-        const int32_t idx[3] = {a, b, c};
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            ok = ok && __builtin_isfinite(verts[3 * (int64_t)idx[k]]) && __builtin_isfinite(verts[3 * (int64_t)idx[k] + 1]) &&
-                 __builtin_isfinite(verts[3 * (int64_t)idx[k] + 2]);
-    }
-    keep[t] = ok ? 1u : 0u;
-}
-
-// after the exclusive scan of keep: the six pairs of kept triangle number m at 6 m ..: key = dst, value = the slot 6 t + k
-__global__ void __launch_bounds__(ST) smooth_emit_kernel(int64_t F, const int32_t* __restrict__ tris, const uint32_t* __restrict__ pos,
+// after the exclusive scan of keep (mesh_topology.h): the six pairs of kept triangle number m at 6 m ..: key = dst, value = the slot 6 t + k
+__global__ void __launch_bounds__(ST) smooth_emit_kernel(int64_t F, SmoothKey key_of, const uint32_t* __restrict__ pos,
                                                          const uint32_t* __restrict__ total, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     const int64_t t = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (t >= F) return;
-    const uint32_t m = pos[t], next = t + 1 < F ? pos[t + 1] : *total;
-    if (next == m) return;
+    if (t >= F || !scanned_flag(pos, total, t, F)) return;
+    const uint32_t m = pos[t];
 #pragma unroll
     for (uint32_t k = 0; k < 6; k++) {
-        uint32_t src, dst;
-        smooth_slot(tris, 6u * (uint32_t)t + k, &src, &dst);
-        key[6 * (int64_t)m + k] = dst;
+        key[6 * (int64_t)m + k] = key_of(6u * (uint32_t)t + k, 0);
         val[6 * (int64_t)m + k] = 6u * (uint32_t)t + k;
     }
-}
-
-__global__ void __launch_bounds__(ST) smooth_key_src_kernel(int64_t n, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val,
-                                                            uint32_t* __restrict__ key) {
-    const int64_t j = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (j >= n) return;
-    uint32_t src, dst;
-    smooth_slot(tris, val[j], &src, &dst);
-    key[j] = src;
 }
 
 // head[j] = 1 where sorted slot j opens a run of equal (src, dst)
@@ -85,9 +63,8 @@ __global__ void __launch_bounds__(ST) smooth_edge_kernel(int64_t n, const int32_
                                                          const uint32_t* __restrict__ epos, const uint32_t* __restrict__ etotal,
                                                          uint32_t* __restrict__ esrc, int32_t* __restrict__ neighbors, uint32_t* __restrict__ estart) {
     const int64_t j = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t e = epos[j], next = j + 1 < n ? epos[j + 1] : *etotal;
-    if (next == e) return;
+    if (j >= n || !scanned_flag(epos, etotal, j, n)) return;
+    const uint32_t e = epos[j];
     uint32_t src, dst;
     smooth_slot(tris, order[j], &src, &dst);
     esrc[e] = src;
@@ -137,11 +114,8 @@ __global__ void __launch_bounds__(ST) smooth_flags_kernel(int64_t V, const int32
         flags[v] = (uint8_t)((c[2] ? SURFEL_SMOOTH_BOUNDARY : 0) | (c[1] ? SURFEL_SMOOTH_NONMANIFOLD : 0) | (c[3] ? SURFEL_SMOOTH_ISOLATED : 0));
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) c[k] += (uint32_t)__shfl_xor((int)c[k], off, 64);
-        c[4] = max(c[4], (uint32_t)__shfl_xor((int)c[4], off, 64));
-    }
+    for (int k = 0; k < 4; k++) c[k] = wave_sum(c[k]);
+    c[4] = wave_max(c[4]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -256,14 +230,7 @@ int64_t surfel_smooth_adjacency(surfel_alloc_fn alloc, void* user, int64_t V, in
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t kept = 0, E2 = 0, tally[5] = {0, 0, 0, 0, 0};
     ScanBuf keep;
-    if (F > 0 && V > 0) {
-        keep = take_scan(alloc, user, F);
-        if (!keep.flags) return api_fail(SURFEL_E_ALLOC, what);
-        hipLaunchKernelGGL(smooth_keep_kernel, dim3(grid(F)), dim3(ST), 0, st, F, V, verts, tris, keep.flags);
-        keep.scan(st);
-        if (int rc = read_words(what, keep.total, &kept, 1, st)) return rc;      // (the sort is sized by the kept triangles)
-        if (int rc = launched("smooth_keep_kernel")) return rc;
-    }
+    if (int rc = mesh_keep(what, alloc, user, V, F, verts, tris, &keep, &kept, st)) return rc;
     if (kept > 0) {
         const int64_t n = 6 * (int64_t)kept;
         SortPairs s(alloc, user, n);
@@ -272,11 +239,10 @@ int64_t surfel_smooth_adjacency(surfel_alloc_fn alloc, void* user, int64_t V, in
         uint32_t* estart = take<uint32_t>(alloc, user, n);
         uint32_t* dtally = take<uint32_t>(alloc, user, 5);
         if (!s.ok() || !head.flags || !esrc || !estart || !dtally) return api_fail(SURFEL_E_ALLOC, what);
-        hipLaunchKernelGGL(smooth_emit_kernel, dim3(grid(F)), dim3(ST), 0, st, F, tris, keep.flags, keep.total, s.ka, s.va);
-        // (src, dst) as two stable LSD sorts: the low word dst, then the high word src, bit_length(V - 1) bits each
-        if (s.sort(bit_length(V - 1), st) < 0) return api_fail(SURFEL_E_LIMIT, "smooth_adjacency: sort");
-        hipLaunchKernelGGL(smooth_key_src_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, s.va, s.ka);
-        if (s.sort(bit_length(V - 1), st) < 0) return api_fail(SURFEL_E_LIMIT, "smooth_adjacency: sort");
+        const SmoothKey key_of{tris};
+        const int bits[2] = {bit_length(V - 1), bit_length(V - 1)};
+        hipLaunchKernelGGL(smooth_emit_kernel, dim3(grid(F)), dim3(ST), 0, st, F, key_of, keep.flags, keep.total, s.ka, s.va);
+        if (int rc = sort_words(s, key_of, 2, bits, "smooth_adjacency: sort", st)) return rc;
         hipLaunchKernelGGL(smooth_head_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, s.va, head.flags);
         head.scan(st);
         hipLaunchKernelGGL(smooth_edge_kernel, dim3(grid(n)), dim3(ST), 0, st, n, tris, s.va, head.flags, head.total, esrc, neighbors, estart);

@@ -5,7 +5,7 @@
 
 #include "../../include/surfel_mesh.h"
 #include "mesh_mc.h"
-#include "side_util.h"
+#include "mesh_topology.h"
 
 namespace surfel {
 
@@ -278,22 +278,23 @@ __global__ void __launch_bounds__(MT) mesh_emit_kernel(Vol v, const int32_t* __r
 // (min, max) key of edge e; an edge with an endpoint outside [0, V) (a negative id is a large unsigned one) gets the key (V, V), which
 // sorts behind every valid group and links nothing
 __device__ inline uint64_t edge_key(const int32_t* tris, uint32_t e, uint32_t V) {
-    const uint32_t t = e / 3, j = e % 3;
-    const uint32_t a = (uint32_t)tris[3 * t + j], b = (uint32_t)tris[3 * t + (j + 1) % 3];
+    uint32_t a, b;
+    half_edge_ends(tris, e, &a, &b);
     if (a >= V || b >= V) return (uint64_t)V << 32 | V;
     return a < b ? ((uint64_t)a << 32 | b) : ((uint64_t)b << 32 | a);
 }
 
-__global__ void __launch_bounds__(MT) edge_keys_kernel(int64_t F, uint32_t V, const int32_t* __restrict__ tris, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+struct EdgeKey {      // the sort's key of an edge: word 0 = max, word 1 = min
+    const int32_t* tris;
+    uint32_t V;
+    __device__ uint32_t operator()(uint32_t e, int word) const { return key_word(edge_key(tris, e, V), word); }
+};
+
+__global__ void __launch_bounds__(MT) edge_keys_kernel(int64_t F, EdgeKey key_of, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     const int64_t e = (int64_t)blockIdx.x * MT + threadIdx.x;
     if (e >= 3 * F) return;
-    key[e] = (uint32_t)edge_key(tris, (uint32_t)e, V);      // the low half of the (min, max) key: sorted first
+    key[e] = key_of((uint32_t)e, 0);      // the low half of the (min, max) key: sorted first
     val[e] = (uint32_t)e;
-}
-
-__global__ void __launch_bounds__(MT) edge_hi_kernel(int64_t n, uint32_t V, const int32_t* __restrict__ tris, const uint32_t* __restrict__ val, uint32_t* __restrict__ key) {
-    const int64_t k = (int64_t)blockIdx.x * MT + threadIdx.x;
-    if (k < n) key[k] = (uint32_t)(edge_key(tris, val[k], V) >> 32);
 }
 
 __device__ inline int32_t uf_find(const int32_t* parent, int32_t x) {
@@ -527,10 +528,10 @@ int surfel_mesh_clusters(surfel_alloc_fn alloc, void* user, int64_t V, int64_t F
     if (!s.ok() || !parent) return api_fail(SURFEL_E_ALLOC, "mesh_clusters: allocator returned NULL");
     // (min, max) keys as two stable LSD sorts of 32-bit halves: max first, then min; bit_length(V) bits each, for the ids 0 .. V - 1
     // and the key V of the edges with an id out of range
-    hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, (uint32_t)V, tris, s.ka, s.va);
-    if (s.sort(bit_length(V), st) < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
-    hipLaunchKernelGGL(edge_hi_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, s.va, s.ka);
-    if (s.sort(bit_length(V), st) < 0) return api_fail(SURFEL_E_LIMIT, "mesh_clusters: sort");
+    const EdgeKey key_of{tris, (uint32_t)V};
+    const int bits[2] = {bit_length(V), bit_length(V)};
+    hipLaunchKernelGGL(edge_keys_kernel, dim3(grid(n)), dim3(MT), 0, st, F, key_of, s.ka, s.va);
+    if (int rc = sort_words(s, key_of, 2, bits, "mesh_clusters: sort", st)) return rc;
     hipLaunchKernelGGL(uf_init_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, size);
     hipLaunchKernelGGL(uf_hook_kernel, dim3(grid(n)), dim3(MT), 0, st, n, (uint32_t)V, tris, s.va, parent);
     hipLaunchKernelGGL(uf_jump_kernel, dim3(grid(F)), dim3(MT), 0, st, F, parent, label);

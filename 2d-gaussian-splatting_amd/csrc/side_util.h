@@ -1,5 +1,6 @@
-// side_util.h — host helpers shared by the modules beside the rasterizer (mesh, evaluation, metrics, scene, frames, viewer), and the
-// exclusive scan of device_scan.hip.
+// side_util.h — helpers shared by the modules beside the rasterizer (mesh, evaluation, metrics, scene, frames, viewer): launch, allocation
+// and read-back on the host, the exclusive scan of device_scan.hip with the test that reads its result, and the sort workspace with the
+// stable sort on a key of several words.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +51,11 @@ inline ScanBuf take_scan(surfel_alloc_fn alloc, void* user, int64_t n, int64_t e
     return p ? ScanBuf(p, p + n, n) : ScanBuf();
 }
 
+// after scan(): was element i of the n flagged (pos = the scanned flags)
+__device__ __forceinline__ bool scanned_flag(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ total, int64_t i, int64_t n) {
+    return (i + 1 < n ? pos[i + 1] : *total) != pos[i];
+}
+
 // Two key / value buffer pairs for n pairs and the sort's scratch.  The caller fills (ka, va); after sort() (ka, va) name the sorted
 // pairs, whichever buffers the last pass wrote.
 struct SortPairs {
@@ -67,5 +73,29 @@ struct SortPairs {
         return r < 0 ? r : 0;
     }
 };
+
+// A stable sort on a key of several 32-bit words, least significant first.  KeyOf is a small struct of pointers with
+// __device__ uint32_t operator()(uint32_t value, int word) const: word `word` of the key of the element a pair's value names.
+constexpr int REKEY_T = 256;      // threads per workgroup
+
+__device__ __forceinline__ uint32_t key_word(uint64_t key, int word) { return (uint32_t)(key >> (32 * word)); }
+
+template <class KeyOf>
+__global__ void __launch_bounds__(REKEY_T) rekey_kernel(int64_t n, const uint32_t* __restrict__ val, uint32_t* __restrict__ key, KeyOf key_of, int word) {
+    const int64_t j = (int64_t)blockIdx.x * REKEY_T + threadIdx.x;
+    if (j < n) key[j] = key_of(val[j], word);
+}
+
+// The caller has filled (s.ka, s.va) with word 0 of every key and its value.  Word w is sorted on bits[w] bits; the words above 0 are
+// written from the values by one launch each.  Fails with SURFEL_E_LIMIT and `what`.
+template <class KeyOf>
+int sort_words(SortPairs& s, KeyOf key_of, int words, const int* bits, const char* what, hipStream_t st) {
+    if (s.n <= 0) return 0;
+    for (int w = 0; w < words; w++) {
+        if (w > 0) hipLaunchKernelGGL(rekey_kernel<KeyOf>, dim3(blocks_for(s.n, REKEY_T)), dim3(REKEY_T), 0, st, s.n, s.va, s.ka, key_of, w);
+        if (s.sort(bits[w], st) < 0) return api_fail(SURFEL_E_LIMIT, what);
+    }
+    return 0;
+}
 
 }  // namespace surfel

@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "../../include/surfel_log.h"
+#include "block_ops.h"
 #include "log_jet_table.h"
 #include "side_util.h"
 #include "vis_pixels.h"
@@ -82,11 +83,7 @@ __global__ void __launch_bounds__(LP_T) log_minmax_kernel(int64_t hw, const floa
                 hi = max(hi, k);
             }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, off, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, off, 64));
-    }
+    lo = wave_min(lo); hi = wave_max(hi);
     if ((threadIdx.x & 63) == 0) {
         s_lo[threadIdx.x >> 6] = lo;
         s_hi[threadIdx.x >> 6] = hi;

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/surfel_view.h"
+#include "block_ops.h"
 #include "side_util.h"
 #include "vis_pixels.h"
 #include "vis_turbo_table.h"
@@ -33,11 +34,7 @@ __global__ void view_reset_kernel(uint32_t* __restrict__ keys) {
 // min and one atomic max by thread 0.  Every thread of the workgroup calls it.
 __device__ __forceinline__ void merge_keys(uint32_t lo, uint32_t hi, uint32_t* __restrict__ keys) {
     __shared__ uint32_t s_lo[VW_T / 64], s_hi[VW_T / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, off, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, off, 64));
-    }
+    lo = wave_min(lo); hi = wave_max(hi);
     if ((threadIdx.x & 63) == 0) {
         s_lo[threadIdx.x >> 6] = lo;
         s_hi[threadIdx.x >> 6] = hi;

@@ -17,12 +17,13 @@ def main():
     tmp = tempfile.mkdtemp(prefix="surfel_rev_")
     subprocess.check_call("git archive %s 2d-gaussian-splatting_amd/csrc include | tar -x -C %s" % (rev, tmp), shell=True, cwd=REPO)
     csrc = os.path.join(tmp, "2d-gaussian-splatting_amd", "csrc")
-    srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith(".hip")]
+    srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp"))]      # (log_events.cpp: load() binds its entry points too)
     objs = []
     for src in srcs:
         obj = os.path.join(tmp, src + ".o")
         objs.append(obj)
         subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + B.FLAGS + defs + B.EXTRA.get(src, []) + ["-c", os.path.join(csrc, src), "-o", obj])
+    os.makedirs(os.path.join(REPO, "2d-gaussian-splatting_amd", "lib"), exist_ok=True)
     lib = os.path.join(REPO, "2d-gaussian-splatting_amd", "lib", "libsurfel_hip_%s.so" % tag)
     subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
     print(lib)

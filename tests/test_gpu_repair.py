@@ -1,6 +1,7 @@
 """GPU checks of the mesh repair (include/surfel_repair.h, REPAIR.md): on every fixture and cap all integer outputs and the counts equal
 the numpy restatement (tests/repair_oracle.py) exactly, positions and colours equal it as bit patterns; the vertex adjacency of the
-output (mesh_smooth.hip, which shares no code with the repair) finds no non-manifold edge and the border the counts name; run-to-run
+output (mesh_smooth.hip, which shares rule 1 and the sort's helper with the repair, nothing else) finds no non-manifold edge and the
+border the counts name; one mesh that fails rule 1 in every way, on which both modules keep the same triangles; run-to-run
 identity, untouched inputs, canaries around every output buffer, border_loops against repair_mesh(max_hole_edges=0), and both CLIs end
 to end."""
 import math
@@ -80,6 +81,28 @@ def test_default_cap_and_a_cap_given_as_a_float():
     _same(got, stats, TC.result("punched", 32), "default")
     got, stats = P.repair_mesh(_mesh(v, t, c), max_hole_edges=4.0)
     _same(got, stats, TC.result("punched", 4), "4.0")
+
+
+def test_smooth_and_repair_keep_the_same_triangles():
+    """rule 1 has one kernel for both modules (csrc/mesh_topology.h): on a mesh with a triangle for each way to fail it — an index below
+    0, an index V, a repeated index, a NaN, a +inf and a -inf vertex, each in another coordinate — the adjacency and the repair keep the
+    same two triangles, and both equal their restatements"""
+    import smooth_oracle as SO
+    import surfel_repair as P
+    import surfel_smooth
+    nan, inf = float("nan"), float("inf")
+    v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [2, nan, 2], [3, 3, inf], [-inf, 4, 4]], np.float32)
+    t = np.array([[0, 1, 3], [0, 1, 2], [-1, 1, 2], [1, 2, 4], [0, 1, 6], [0, 2, 1], [2, 1, 1], [2, 0, 5]], np.int32)
+    V, F = len(v), len(t)
+    assert (V, F) == (6, 8) and SO.kept_triangles(v, t).tolist() == [False, True, False, False, False, True, False, False]
+    want_adj, want_rep = SO.adjacency(v, t)["stats"], O.repair(v, t, None, 0)["stats"]
+    assert (want_adj["kept"], want_adj["dropped"]) == (want_rep["kept"], want_rep["dropped"]) == (2, 6)      # the two restatements agree
+    mesh = _mesh(v, t)
+    adj = surfel_smooth.mesh_adjacency(mesh).stats
+    rep = P.repair_mesh(mesh, 0)[1]
+    print("adjacency %s, repair %s" % (adj, {k: rep[k] for k in O.COUNTS}))
+    assert (adj["kept"], adj["dropped"]) == (2, 6) and (rep["kept"], rep["dropped"]) == (2, 6)
+    assert adj == want_adj and {k: rep[k] for k in O.COUNTS} == want_rep
 
 
 # ------------------------------------------------------------------------------------------------ 2: border_loops

@@ -316,8 +316,8 @@ def test_tnt_kernels_no_scratch():
     sys.path.insert(0, os.path.join(REPO, "scripts"))
     import isa_count
     ks = isa_count.kernels(isa_count.assemble("eval_tnt.hip"))
-    names = [k for k in ks if "tnt_" in k]
-    assert len(names) == 10, names
+    names = [k for k in ks if "tnt_" in k or "rekey_kernel" in k]      # (the voxel sort's high word: rekey_kernel<VoxelKey>, side_util.h)
+    assert len(names) == 10 and sum("rekey_kernel" in k for k in names) == 1, names
     for k in names:
         assert int(ks[k][1].get("private_segment_fixed_size", 0)) == 0, k
     sums = [k for k in names if "corr_sums_kernel" in k][0]
