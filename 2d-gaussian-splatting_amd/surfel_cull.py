@@ -10,6 +10,7 @@ host reads trajectories, inverts the 4 x 4 poses in fp32 and writes the culled m
 """
 import argparse
 import ctypes as C
+import functools
 import json
 import os
 import sys
@@ -19,7 +20,7 @@ import torch
 
 import surfel_native as _n
 import surfel_eval as _e
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, mesh_arrays, read_mesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -33,17 +34,8 @@ TNT_INTRINSICS = (1163.8678928442187, 1172.793101201448, 962.3120628412543, 542.
 SMALL_PIXELS = 32               # SURFEL_CULL_SMALL_PIXELS of include/surfel_cull.h
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_cull: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _points(t, what):
-    t = _dev(t, what)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("surfel_cull: %s must be [N, 3], got %s" % (what, list(t.shape)))
-    return t.detach().to(torch.float32).contiguous()
+_dev = functools.partial(_n.device_tensor, "surfel_cull")
+_points = functools.partial(_n.rows, "surfel_cull", dtype=torch.float32)
 
 
 def _cameras(w2c, intrinsics, dev):
@@ -66,10 +58,7 @@ def mesh_depth(mesh, w2c, intrinsics, H, W, znear=ZNEAR, zfar=ZFAR, small_pixels
     intrinsics: (fx, fy, cx, cy) for all views or [V, 4].  small_pixels: the size-class threshold (a test argument: the images do not
     depend on it).  timings: a dict that receives ms of the small-class, large-class and other launches and the number of (view,
     triangle) pairs of the large class (synchronises)."""
-    verts = _points(mesh.vertices, "mesh.vertices")
-    tris = _dev(mesh.triangles, "mesh.triangles").detach().to(torch.int32).contiguous()
-    if tris.ndim != 2 or tris.shape[1] != 3:
-        raise ValueError("surfel_cull: mesh.triangles must be [F, 3], got %s" % list(tris.shape))
+    verts, tris = mesh_arrays("surfel_cull", mesh, shapes=("[N, 3]", "[F, 3]"))
     dev = verts.device
     w, k = _cameras(w2c, intrinsics, dev)
     depth = torch.empty((w.shape[0], int(H), int(W)), dtype=torch.float32, device=dev)
@@ -250,8 +239,7 @@ def main(argv=None):
     if (args.traj_path is None) == (args.model_path is None):
         raise SystemExit("give --traj-path or -m MODEL_DIR")
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+    mesh = read_mesh(args.ply_path, dev)
     if args.model_path is not None:
         cams = read_model_cameras(args.model_path)
         out = cull_mesh_cameras(mesh, cams, args.min_views, args.eps, args.near, args.far)
@@ -261,10 +249,10 @@ def main(argv=None):
         out = cull_mesh_views(mesh, poses, (args.fx, args.fy, args.cx, args.cy), args.height, args.width, args.convention, args.min_views, args.eps,
                               args.near, args.far)
         views = len(poses)
-    stem = args.ply_path[:-4] if args.ply_path.endswith(".ply") else args.ply_path
+    stem = surfel_io.ply_stem(args.ply_path)
     surfel_io.write_triangle_mesh(stem + "_cull.ply", out)
-    print("%d views: kept %d of %d vertices, %d of %d triangles -> %s" % (views, out.vertices.shape[0], v.shape[0], out.triangles.shape[0], t.shape[0],
-                                                                        stem + "_cull.ply"))
+    print("%d views: kept %d of %d vertices, %d of %d triangles -> %s" % (views, out.vertices.shape[0], mesh.vertices.shape[0], out.triangles.shape[0],
+                                                                        mesh.triangles.shape[0], stem + "_cull.ply"))
     return out
 
 

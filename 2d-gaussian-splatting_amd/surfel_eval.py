@@ -10,6 +10,7 @@ the shuffle order and the final sums cross the host boundary.  No CPU path: CPU 
 """
 import argparse
 import ctypes as C
+import functools
 import json
 import math
 import os
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 import surfel_native as _n
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, read_mesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -29,17 +30,8 @@ MAX_CELLS = 1 << 27          # cells of one grid (8 B each), and at most 64 per 
 THIN_CELL = 1.0 + 1.0 / 512  # cell edge of the thinning grid in units of density (the library asks for 1 + 2^-10)
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_eval: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _points(t, what):
-    t = _dev(t, what)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("surfel_eval: %s must be [N, 3], got %s" % (what, list(t.shape)))
-    return t.detach().to(torch.float32).contiguous()
+_dev = functools.partial(_n.device_tensor, "surfel_eval")
+_points = functools.partial(_n.rows, "surfel_eval", dtype=torch.float32)
 
 
 # ------------------------------------------------------------------------------------------------ rule 1: sampling
@@ -371,8 +363,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     if args.mode == "mesh":
-        v, t, c = surfel_io.read_triangle_mesh(args.data)
-        data = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+        data = read_mesh(args.data, dev)
     else:
         p = surfel_io.read_ply(args.data)
         data = torch.from_numpy(np.stack([p["x"], p["y"], p["z"]], 1).astype(np.float32)).to(dev)

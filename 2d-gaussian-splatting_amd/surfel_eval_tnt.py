@@ -11,6 +11,7 @@ boundary, and the host does the 3 x 3 / 4 x 4 algebra, file I/O and the camera-c
 """
 import argparse
 import ctypes as C
+import functools
 import json
 import math
 import os
@@ -21,7 +22,7 @@ import torch
 
 import surfel_native as _n
 import surfel_eval as _e
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, read_mesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -35,17 +36,8 @@ SCENES_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse":
 RELATIVE_FITNESS, RELATIVE_RMSE, MAX_ITERATION = 1e-6, 20.0, 30
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_eval_tnt: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _points(t, what):
-    t = _dev(t, what)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("surfel_eval_tnt: %s must be [N, 3], got %s" % (what, list(t.shape)))
-    return t.detach().to(torch.float32).contiguous()
+_dev = functools.partial(_n.device_tensor, "surfel_eval_tnt")
+_points = functools.partial(_n.rows, "surfel_eval_tnt", dtype=torch.float32)
 
 
 def _mat4(T):
@@ -441,7 +433,6 @@ def _cloud_of_ply(path, dev):
 
 
 def main(argv=None):
-    import surfel_io
     ap = argparse.ArgumentParser(description="Tanks-and-Temples F-score of a mesh (the reference's scripts/eval_tnt/run.py)")
     ap.add_argument("--dataset-dir", type=str, required=True, help="DIR/SCENE holding SCENE.ply, SCENE.json, SCENE_COLMAP_SfM.log, SCENE_trans.txt")
     ap.add_argument("--traj-path", type=str, required=True, help="estimated trajectory (.log or .npy)")
@@ -460,8 +451,7 @@ def main(argv=None):
     tau = SCENES_TAU[scene] if args.tau is None else args.tau
     out_dir = args.out_dir.strip() or os.path.join(os.path.dirname(args.ply_path), "evaluation")
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+    mesh = read_mesh(args.ply_path, dev)
     base = os.path.join(args.dataset_dir, scene)
     res = evaluate_tnt(mesh, _cloud_of_ply(base + ".ply", dev), read_crop_volume(base + ".json"), tau, est_traj=read_trajectory(args.traj_path),
                        gt_traj=read_trajectory(base + "_COLMAP_SfM.log"), gt_trans=read_alignment(base + "_trans.txt"), seed=args.seed,

@@ -148,6 +148,11 @@ def read_triangle_mesh(path):
     return verts, tris, cols
 
 
+def ply_stem(path):
+    """MESH of MESH.ply: what the mesh tools append _smoothed.ply, _cull.ply, ... to; any other path as it is"""
+    return path[:-4] if path.endswith(".ply") else path
+
+
 def write_obj(path, vertices, triangles, vt=None, texture=None):
     """Wavefront OBJ of a mesh (numpy arrays or tensors): `v x y z` per vertex, `f a b c` per triangle (1-based).  vt [F, 3, 2]: three
     texture coordinates per triangle in OBJ's convention (the origin at the image's lower left corner), written as 3 F `vt u v` lines

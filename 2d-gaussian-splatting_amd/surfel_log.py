@@ -106,15 +106,9 @@ def encode_steps(records, iter_time_ms, wall_time):
 
 
 # ------------------------------------------------------------------------------------------------ the device parts
-def _device_tensor(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_log: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
 def append(state, ring, iteration, points, scalars, lambda_normal, lambda_dist):
     """surfel_log_append: one record into ring (uint8 [capacity * 32]) behind whatever the current stream holds"""
-    _device_tensor(scalars, "scalars")
+    _n.device_tensor("surfel_log", scalars, "scalars")
     if scalars.dtype != torch.float32 or scalars.numel() < 6 or not scalars.is_contiguous():
         raise ValueError("surfel_log.append: six contiguous float32 scalars expected")
     _n.call(scalars.device, "surfel_log_append", state, ring, ring.numel() // RECORD_BYTES, int(iteration), int(points), scalars,
@@ -126,7 +120,7 @@ def panel(mode, planes, out=None, scratch=None):
     mode: "rgb" and "normal" take three planes, "gray", "turbo_max" and "jet_minmax" one.  Nothing waits for the device."""
     if mode not in MODES:
         raise ValueError("surfel_log.panel: mode must be one of %s" % ", ".join(MODES))
-    t = _device_tensor(planes, "planes").detach()
+    t = _n.device_tensor("surfel_log", planes, "planes").detach()
     if t.dtype != torch.float32:
         raise ValueError("surfel_log.panel: float32 planes expected, got %s" % t.dtype)
     if t.dim() == 2:

@@ -36,6 +36,39 @@ class TriangleMesh:
         return TriangleMesh(*(np.asarray(x.cpu().numpy() if torch.is_tensor(x) else x) for x in (self.vertices, self.triangles, self.vertex_colors)))
 
 
+def read_mesh(path, device):
+    """the TriangleMesh of a .ply (surfel_io.read_triangle_mesh) on `device`"""
+    import surfel_io
+    return TriangleMesh(*(torch.from_numpy(a).to(device) for a in surfel_io.read_triangle_mesh(path)))
+
+
+def mesh_arrays(who, mesh, colors=False, shapes=("[N, 3]", "[N, 3]")):
+    """What a side module's kernels take of a mesh, checked in this order: (vertices fp32 [V, 3], triangles int32 [F, 3]), contiguous on
+    the device; with colors also mesh.vertex_colors as fp32 [V, 3], or None where the mesh has none.  who: the calling module's name, the
+    messages' prefix; shapes: how its messages write the two shapes."""
+    verts = _n.rows(who, mesh.vertices, "mesh.vertices", torch.float32, shapes[0])
+    tris = _n.rows(who, mesh.triangles, "mesh.triangles", torch.int32, shapes[1])
+    if not colors:
+        return verts, tris
+    cols = getattr(mesh, "vertex_colors", None)
+    if cols is not None:
+        cols = _n.rows(who, cols, "mesh.vertex_colors", torch.float32)
+        if cols.shape[0] != verts.shape[0]:
+            raise ValueError("%s: %d colours for %d vertices" % (who, cols.shape[0], verts.shape[0]))
+    return verts, tris, cols
+
+
+def shown_colors(who, mesh, V):
+    """mesh.vertex_colors as the modules that draw a mesh take them: fp32 [V, 3] on the device, None where the mesh has none or empty ones"""
+    c = getattr(mesh, "vertex_colors", None)
+    if c is None or c.numel() == 0:
+        return None
+    c = _n.device_tensor(who, c, "mesh.vertex_colors")
+    if tuple(c.shape) != (V, 3):
+        raise ValueError("%s: mesh.vertex_colors must be [V, 3], got %s" % (who, list(c.shape)))
+    return c.detach().to(torch.float32).contiguous()
+
+
 # ------------------------------------------------------------------------------------------------ cameras
 def camera_intrinsics(cam):
     """(fx, fy, cx, cy) as utils/mesh_utils.py:43-68: (projection_matrix @ ndc2pix)[:3,:3].T with cx = (W-1)/2, cy = (H-1)/2."""
@@ -560,8 +593,7 @@ def main(argv=None):
 
     if args.skip_mesh:
         if args.render_path and args.render_mesh:
-            v, t, c = surfel_io.read_triangle_mesh(os.path.join(out, post_name))
-            render_mesh_path(TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev)))
+            render_mesh_path(read_mesh(os.path.join(out, post_name), dev))
         return 0
     gaussians.active_sh_degree = 0      # render.py:91: diffuse colour only
     ext.reconstruction(cams)

@@ -10,6 +10,7 @@ operation order.  The mesh, the keys and the frames stay on the device.  No CPU 
 """
 import argparse
 import ctypes as C
+import functools
 import math
 import os
 import sys
@@ -20,7 +21,7 @@ import torch
 import surfel_native as _n
 import surfel_cull as _c
 import surfel_path as _sp
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, mesh_arrays, read_mesh, shown_colors  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -34,30 +35,8 @@ NORMAL_SCALE = 1 << 20                                     # SURFEL_MESHVIEW_NOR
 EMPTY_KEY = (0x7f800000 << 32) | 0xffffffff                # SURFEL_MESHVIEW_EMPTY
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_meshview: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _mesh_arrays(mesh):
-    verts = _dev(mesh.vertices, "mesh.vertices")
-    if verts.ndim != 2 or verts.shape[1] != 3:
-        raise ValueError("surfel_meshview: mesh.vertices must be [V, 3], got %s" % list(verts.shape))
-    tris = _dev(mesh.triangles, "mesh.triangles")
-    if tris.ndim != 2 or tris.shape[1] != 3:
-        raise ValueError("surfel_meshview: mesh.triangles must be [F, 3], got %s" % list(tris.shape))
-    return verts.detach().to(torch.float32).contiguous(), tris.detach().to(torch.int32).contiguous()
-
-
-def _colors(mesh, V):
-    c = getattr(mesh, "vertex_colors", None)
-    if c is None or c.numel() == 0:
-        return None
-    c = _dev(c, "mesh.vertex_colors")
-    if tuple(c.shape) != (V, 3):
-        raise ValueError("surfel_meshview: mesh.vertex_colors must be [V, 3], got %s" % list(c.shape))
-    return c.detach().to(torch.float32).contiguous()
+_dev = functools.partial(_n.device_tensor, "surfel_meshview")
+_mesh_arrays = functools.partial(mesh_arrays, "surfel_meshview", shapes=("[V, 3]", "[F, 3]"))
 
 
 def _device_cameras(w2c, intrinsics, dev):
@@ -131,7 +110,7 @@ def shade(mesh, key, w2c, sample_intrinsics, H, W, ssaa=1, mode="shaded", normal
     w, k = _device_cameras(w2c, sample_intrinsics, dev)
     if w.shape[0] != key.shape[0]:
         raise ValueError("surfel_meshview: %d cameras for %d key images" % (w.shape[0], key.shape[0]))
-    cols = _colors(mesh, verts.shape[0]) if albedo == "color" else None
+    cols = shown_colors("surfel_meshview", mesh, verts.shape[0]) if albedo == "color" else None
     if normals is not None:
         normals = _dev(normals, "normals")
         if tuple(normals.shape) != (verts.shape[0], 3):
@@ -416,8 +395,7 @@ def main(argv=None):
         texture = surfel_texture.load_textured_mesh(args.ply_path, dev)
         mesh = texture.mesh
     else:
-        v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-        mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+        mesh = read_mesh(args.ply_path, dev)
     if TEXTURED in args.mesh_modes and texture is None:
         raise SystemExit("--mesh_modes textured needs an .obj with a texture")
     stem = args.ply_path[:-4] if args.ply_path.endswith((".ply", ".obj")) else args.ply_path

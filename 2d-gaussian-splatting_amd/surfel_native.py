@@ -4,6 +4,9 @@ There is NO fallback: if the HIP library is missing or cannot be loaded this mod
 GPU box can never silently run some other path.  torch is imported first so that the HIP runtime
 already mapped by PyTorch-ROCm (same SONAME libamdhip64.so.7) is the one our library binds to; torch
 here is plumbing only (device memory through its caching allocator, current stream).
+
+Adding a side module: check its tensors with device_tensor / rows below ("no CPU path: CPU tensors raise" is stated there, once),
+and take a mesh with surfel_mesh.mesh_arrays.
 """
 import ctypes as C
 import math
@@ -439,6 +442,28 @@ class TorchAllocator:
 
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# ------------------------------------------------------------------------------------------------ argument checks of the side modules
+# (`who` is the calling module's name, the prefix of every message)
+def device_tensor(who, t, what):
+    """t, or "no CPU path: CPU tensors raise": RuntimeError for anything but a tensor on a HIP device"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("%s: tensors must live on a HIP device (%s: got %s)" % (who, what, t.device if torch.is_tensor(t) else type(t).__name__))
+    return t
+
+
+def rows(who, t, what, dtype, shape="[N, 3]"):
+    """t as a contiguous [N, 3] device tensor of `dtype`, detached; ValueError for another shape.  shape: how the message writes [N, 3]"""
+    t = device_tensor(who, t, what)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("%s: %s must be %s, got %s" % (who, what, shape, list(t.shape)))
+    return t.detach().to(dtype).contiguous()
+
+
+def counts_dict(names, carray):
+    """{name: int} of a ctypes array of counts the library filled"""
+    return {k: int(v) for k, v in zip(names, carray)}
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

@@ -18,7 +18,7 @@ import sys
 import torch
 
 import surfel_native as _n
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, mesh_arrays, read_mesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -32,19 +32,6 @@ half-edges 3 m + k of the repaired mesh's triangles in ascending order; loop [B]
 from the loop's smallest half-edge; lengths [n_loops] int32; stats: the COUNTS as a dict of ints (nothing filled)."""
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_repair: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _rows(t, what, dtype):
-    t = _dev(t, what)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("surfel_repair: %s must be [N, 3], got %s" % (what, list(t.shape)))
-    return t.detach().to(dtype).contiguous()
-
-
 def check_arguments(max_hole_edges):
     """REPAIR.md §Interface: ValueError for anything but a whole number >= 0 (a bool is no number here).  Returns it as an int."""
     ok = isinstance(max_hole_edges, numbers.Real) and not isinstance(max_hole_edges, bool)      # (numpy's bool_ is no Real)
@@ -55,19 +42,13 @@ def check_arguments(max_hole_edges):
 
 def _analyze(mesh, cap, stage_ms=None):
     """(verts, tris, colors, plan, stats, allocator): rules 1-5 and the fill's sizes; the plan's arrays live in the allocator"""
-    cols = getattr(mesh, "vertex_colors", None)
-    verts = _rows(mesh.vertices, "mesh.vertices", torch.float32)
-    tris = _rows(mesh.triangles, "mesh.triangles", torch.int32)
-    if cols is not None:
-        cols = _rows(cols, "mesh.vertex_colors", torch.float32)
-        if cols.shape[0] != verts.shape[0]:
-            raise ValueError("surfel_repair: %d colours for %d vertices" % (cols.shape[0], verts.shape[0]))
+    verts, tris, cols = mesh_arrays("surfel_repair", mesh, colors=True)
     dev = verts.device
     plan = _n.RepairPlan()
     counts = (C.c_int64 * len(COUNTS))()
     alloc = _n.TorchAllocator(dev)
     _n.call(dev, "surfel_repair_analyze", alloc.cb, None, verts.shape[0], tris.shape[0], verts, tris, cap, C.byref(plan), counts, stage_ms)
-    return verts, tris, cols, plan, {k: int(v) for k, v in zip(COUNTS, counts)}, alloc
+    return verts, tris, cols, plan, _n.counts_dict(COUNTS, counts), alloc
 
 
 def repair_mesh(mesh, max_hole_edges=32, timings=None):
@@ -131,8 +112,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     cap = check_arguments(args.max_hole_edges)
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+    mesh = read_mesh(args.ply_path, dev)
     if args.report:
         loops = border_loops(mesh)
         print(", ".join("%s %d" % (k, loops.stats[k]) for k in COUNTS[:9]))
@@ -145,7 +125,7 @@ def main(argv=None):
             edge = top
         return loops
     out, stats = repair_mesh(mesh, max_hole_edges=cap)
-    stem = args.ply_path[:-4] if args.ply_path.endswith(".ply") else args.ply_path
+    stem = surfel_io.ply_stem(args.ply_path)
     surfel_io.write_triangle_mesh(stem + "_repaired.ply", out)
     print("%s -> %s" % (summary(stats), stem + "_repaired.ply"))
     return out

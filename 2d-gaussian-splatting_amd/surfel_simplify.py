@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 import surfel_native as _n
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, mesh_arrays, read_mesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -24,30 +24,6 @@ LAM = 1e-3                      # the regulariser as a share of the quadric's tr
 N_MAX = 1 << 20                 # the finest grid resolution the bisection tries: its cell indices fit 21 bits
 STAGES = ("keys_ms", "sorts_ms", "sums_solve_ms", "remap_dedupe_ms", "compaction_ms")      # stage_ms of include/surfel_simplify.h
 COUNTS = ("clusters", "vertices", "triangles", "dropped", "collapsed", "duplicates")        # counts of include/surfel_simplify.h
-
-
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_simplify: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _rows(t, what, dtype):
-    t = _dev(t, what)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("surfel_simplify: %s must be [N, 3], got %s" % (what, list(t.shape)))
-    return t.detach().to(dtype).contiguous()
-
-
-def _mesh(mesh):
-    verts = _rows(mesh.vertices, "mesh.vertices", torch.float32)
-    tris = _rows(mesh.triangles, "mesh.triangles", torch.int32)
-    cols = getattr(mesh, "vertex_colors", None)
-    if cols is not None:
-        cols = _rows(cols, "mesh.vertex_colors", torch.float32)
-        if cols.shape[0] != verts.shape[0]:
-            raise ValueError("surfel_simplify: %d colours for %d vertices" % (cols.shape[0], verts.shape[0]))
-    return verts, tris, cols
 
 
 def _cell(cell):
@@ -69,7 +45,7 @@ def _origin(origin):
 def mesh_bounds(vertices):
     """(lo [3], hi [3]) float32 on the host: the component-wise extrema of the vertices whose three coordinates are finite, computed on the
     device; None when no vertex is finite."""
-    verts = _rows(vertices, "vertices", torch.float32)
+    verts = _n.rows("surfel_simplify", vertices, "vertices", torch.float32)
     out = (C.c_float * 6)()
     alloc = _n.TorchAllocator(verts.device)
     if not _n.call(verts.device, "surfel_simplify_bounds", alloc.cb, None, verts.shape[0], verts, out):
@@ -85,7 +61,7 @@ def _bounds_arg(b):
 def vertex_clusters(mesh, cell, origin=None):
     """int32 [V] on the device: per vertex the number of its grid cell among the occupied cells in key order (z, then y, then x), -1 for a
     vertex with a non-finite coordinate (SIMPLIFY.md §Rules 2, 3).  origin: the grid's corner, default the minimum of the finite vertices."""
-    verts = _rows(mesh.vertices, "mesh.vertices", torch.float32)
+    verts = _n.rows("surfel_simplify", mesh.vertices, "mesh.vertices", torch.float32)
     cluster = torch.empty(verts.shape[0], dtype=torch.int32, device=verts.device)
     alloc = _n.TorchAllocator(verts.device)
     _n.call(verts.device, "surfel_simplify_clusters", alloc.cb, None, verts.shape[0], verts, None, _origin(origin), _cell(cell), cluster)
@@ -95,12 +71,12 @@ def vertex_clusters(mesh, cell, origin=None):
 def count_faces(mesh, cell, origin=None, bounds=None):
     """{clusters, triangles, dropped, collapsed, duplicates} of the mesh simplify_mesh would return at this cell size, without the sums,
     the solve and the outputs (SIMPLIFY.md §Rules 8: one probe of the bisection).  bounds: mesh_bounds' result, to spare its kernel."""
-    verts, tris, _ = _mesh(mesh)
+    verts, tris, _ = mesh_arrays("surfel_simplify", mesh, colors=True)
     counts = (C.c_int64 * len(COUNTS))()
     alloc = _n.TorchAllocator(verts.device)
     _n.call(verts.device, "surfel_simplify_count", alloc.cb, None, verts.shape[0], tris.shape[0], verts, tris, _bounds_arg(bounds), _origin(origin),
             _cell(cell), counts)
-    return {k: int(v) for k, v in zip(COUNTS, counts) if k != "vertices"}
+    return {k: v for k, v in _n.counts_dict(COUNTS, counts).items() if k != "vertices"}
 
 
 def grid_cell(bounds, n):
@@ -150,7 +126,7 @@ def simplify_mesh(mesh, cell=None, target_faces=None, origin=None, lam=LAM, timi
     bisection (synchronises)."""
     if (cell is None) == (target_faces is None):
         raise ValueError("surfel_simplify: give cell or target_faces")
-    verts, tris, cols = _mesh(mesh)
+    verts, tris, cols = mesh_arrays("surfel_simplify", mesh, colors=True)
     dev = verts.device
     V, F = verts.shape[0], tris.shape[0]
     stats = {"n": 0, "probes": 0}
@@ -192,7 +168,7 @@ def simplify_mesh(mesh, cell=None, target_faces=None, origin=None, lam=LAM, timi
     alloc = _n.TorchAllocator(dev)
     _n.call(dev, "surfel_simplify_mesh", alloc.cb, None, V, F, verts, cols, tris, _bounds_arg(bounds), _origin(origin), cell, float(lam), cluster,
             cluster_vertex, vout, cout, tout, counts, ms)
-    stats.update({k: int(v) for k, v in zip(COUNTS, counts)})
+    stats.update(_n.counts_dict(COUNTS, counts))
     nv, nf = stats["vertices"], stats["triangles"]
     stats.update(cell=cell, cluster=cluster, cluster_vertex=cluster_vertex[:stats["clusters"]])
     if timings is not None:
@@ -213,14 +189,14 @@ def main(argv=None):
     if sum(x is not None for x in (args.cell, args.faces, args.ratio)) != 1:
         raise SystemExit("give exactly one of --cell, --faces and --ratio")
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
-    target = args.faces if args.faces is not None else (int(args.ratio * t.shape[0]) if args.ratio is not None else None)
+    mesh = read_mesh(args.ply_path, dev)
+    V, F = mesh.vertices.shape[0], mesh.triangles.shape[0]
+    target = args.faces if args.faces is not None else (int(args.ratio * F) if args.ratio is not None else None)
     out, stats = simplify_mesh(mesh, cell=args.cell, target_faces=target, lam=args.lam)
-    stem = args.ply_path[:-4] if args.ply_path.endswith(".ply") else args.ply_path
+    stem = surfel_io.ply_stem(args.ply_path)
     surfel_io.write_triangle_mesh(stem + "_simplified.ply", out)
     print("cell %g (n = %d): %d of %d vertices, %d of %d triangles (%d collapsed, %d duplicates) -> %s" %
-          (stats["cell"], stats["n"], out.vertices.shape[0], v.shape[0], out.triangles.shape[0], t.shape[0], stats["collapsed"], stats["duplicates"],
+          (stats["cell"], stats["n"], out.vertices.shape[0], V, out.triangles.shape[0], F, stats["collapsed"], stats["duplicates"],
            stem + "_simplified.ply"))
     return out
 

@@ -11,13 +11,14 @@ No CPU path: CPU tensors raise.
 import argparse
 import collections
 import ctypes as C
+import functools
 import os
 import sys
 
 import torch
 
 import surfel_native as _n
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, mesh_arrays, read_mesh  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -33,17 +34,8 @@ within each row, multiplicity [E2] int32 (the kept triangles on that edge: 1 a b
 (FLAG_* bits), stats: the COUNTS as a dict of ints."""
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_smooth: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
-
-
-def _rows(t, what, dtype):
-    t = _dev(t, what)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("surfel_smooth: %s must be [N, 3], got %s" % (what, list(t.shape)))
-    return t.detach().to(dtype).contiguous()
+_dev = functools.partial(_n.device_tensor, "surfel_smooth")
+_rows = functools.partial(_n.rows, "surfel_smooth")
 
 
 def check_arguments(iterations, method, lam, mu, boundary):
@@ -71,8 +63,7 @@ def check_arguments(iterations, method, lam, mu, boundary):
 def mesh_adjacency(mesh):
     """Adjacency of mesh.vertices [V, 3] / mesh.triangles [F, 3] (SMOOTH.md §Rules 1-3).  A triangle that names an index outside [0, V),
     repeats an index or names a vertex with a non-finite coordinate contributes nothing.  The same bytes on every run."""
-    verts = _rows(mesh.vertices, "mesh.vertices", torch.float32)
-    tris = _rows(mesh.triangles, "mesh.triangles", torch.int32)
+    verts, tris = mesh_arrays("surfel_smooth", mesh)
     dev = verts.device
     V, F = verts.shape[0], tris.shape[0]
     offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
@@ -82,7 +73,7 @@ def mesh_adjacency(mesh):
     counts = (C.c_int64 * len(COUNTS))()
     alloc = _n.TorchAllocator(dev)
     e2 = _n.call(dev, "surfel_smooth_adjacency", alloc.cb, None, V, F, verts, tris, offsets, neighbors, multiplicity, flags, counts)
-    return Adjacency(offsets, neighbors[:e2], multiplicity[:e2], flags, {k: int(v) for k, v in zip(COUNTS, counts)})
+    return Adjacency(offsets, neighbors[:e2], multiplicity[:e2], flags, _n.counts_dict(COUNTS, counts))
 
 
 def filter_steps(adjacency, attribute, factors, boundary="free"):
@@ -112,6 +103,7 @@ def smooth_mesh(mesh, iterations=10, method="taubin", lam=0.5, mu=-0.53, boundar
     cols = getattr(mesh, "vertex_colors", None)
     if colors and cols is None:
         raise ValueError("surfel_smooth: colors=True needs mesh.vertex_colors")
+    # (not mesh_arrays: the triangles are checked where the adjacency is built, after the colours, and not at all when it is passed in)
     verts = _rows(mesh.vertices, "mesh.vertices", torch.float32)
     if colors and _rows(cols, "mesh.vertex_colors", torch.float32).shape[0] != verts.shape[0]:
         raise ValueError("surfel_smooth: %d colours for %d vertices" % (cols.shape[0], verts.shape[0]))
@@ -148,13 +140,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     check_arguments(args.iterations, args.method, args.lam, args.mu, args.boundary)
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
+    mesh = read_mesh(args.ply_path, dev)
     out, stats = smooth_mesh(mesh, iterations=args.iterations, method=args.method, lam=args.lam, mu=args.mu, boundary=args.boundary, colors=args.colors)
-    stem = args.ply_path[:-4] if args.ply_path.endswith(".ply") else args.ply_path
+    stem = surfel_io.ply_stem(args.ply_path)
     surfel_io.write_triangle_mesh(stem + "_smoothed.ply", out)
     print("%s, %d steps over %d vertices and %d directed edges (%d border, %d non-manifold edges, largest degree %d) -> %s" %
-          (args.method, stats["steps"], v.shape[0], stats["directed_edges"], stats["border_edges"], stats["nonmanifold_edges"], stats["max_degree"],
+          (args.method, stats["steps"], mesh.vertices.shape[0], stats["directed_edges"], stats["border_edges"], stats["nonmanifold_edges"], stats["max_degree"],
            stem + "_smoothed.ply"))
     return out
 

@@ -11,6 +11,7 @@ CPU tensors raise.
 """
 import argparse
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -19,7 +20,7 @@ import torch
 
 import surfel_native as _n
 import surfel_cull as _c
-from surfel_mesh import MeshLimitError, TriangleMesh  # noqa: F401  (MeshLimitError is part of this module's surface)
+from surfel_mesh import MeshLimitError, TriangleMesh, read_mesh, shown_colors  # noqa: F401  (MeshLimitError is part of this module's surface)
 
 _n.load()
 
@@ -45,28 +46,15 @@ def cell_side(c):
     return legs(c) + PAD
 
 
-def _dev(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("surfel_texture: tensors must live on a HIP device (%s: got %s)" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t
+_dev = functools.partial(_n.device_tensor, "surfel_texture")
 
 
-def _mesh(mesh):
+def _mesh(mesh):      # (surfel_mesh.mesh_arrays, but one message names both shapes)
     verts = _dev(mesh.vertices, "mesh.vertices")
     tris = _dev(mesh.triangles, "mesh.triangles")
     if verts.ndim != 2 or verts.shape[1] != 3 or tris.ndim != 2 or tris.shape[1] != 3:
         raise ValueError("surfel_texture: mesh.vertices must be [V, 3] and mesh.triangles [F, 3], got %s and %s" % (list(verts.shape), list(tris.shape)))
     return verts.detach().to(torch.float32).contiguous(), tris.detach().to(torch.int32).contiguous()
-
-
-def _colors(mesh, V):
-    c = getattr(mesh, "vertex_colors", None)
-    if c is None or c.numel() == 0:
-        return None
-    c = _dev(c, "mesh.vertex_colors")
-    if tuple(c.shape) != (V, 3):
-        raise ValueError("surfel_texture: mesh.vertex_colors must be [V, 3], got %s" % list(c.shape))
-    return c.detach().to(torch.float32).contiguous()
 
 
 def _density(density):
@@ -304,7 +292,8 @@ def resolve(mesh, lay, acc, blend="average", background=(0.0, 0.0, 0.0), out=Non
         raise ValueError("surfel_texture: out must be a contiguous uint8 tensor of %d elements" % (lay.height * lay.width * 3))
     stats = torch.empty(2, dtype=torch.int64, device=verts.device)
     bg = [float(x) for x in background]
-    _n.call(verts.device, "surfel_texture_resolve", verts.shape[0], tris.shape[0], verts, tris, _colors(mesh, verts.shape[0]), lay._ctable, lay.order,
+    cols = shown_colors("surfel_texture", mesh, verts.shape[0])
+    _n.call(verts.device, "surfel_texture_resolve", verts.shape[0], tris.shape[0], verts, tris, cols, lay._ctable, lay.order,
             lay.width, lay.height, acc, _blend(blend), bg[0], bg[1], bg[2], out, stats)
     return out.view(lay.height, lay.width, 3), stats
 
@@ -461,9 +450,8 @@ def main(argv=None):
     if args.source == "gt" and args.source_path is None:
         raise SystemExit("--source gt needs -s CAPTURE")
     dev = torch.device("cuda:0")
-    v, t, c = surfel_io.read_triangle_mesh(args.ply_path)
-    mesh = TriangleMesh(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev))
-    stem = args.out or ((args.ply_path[:-4] if args.ply_path.endswith(".ply") else args.ply_path) + "_textured")
+    mesh = read_mesh(args.ply_path, dev)
+    stem = args.out or surfel_io.ply_stem(args.ply_path) + "_textured"
     import surfel_mesh
     import surfel_model
     from surfel_render import render

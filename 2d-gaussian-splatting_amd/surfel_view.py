@@ -318,9 +318,8 @@ def main(argv=None):
         texture = surfel_texture.load_textured_mesh(args.mesh, dev)
         mesh = texture.mesh
     elif args.mesh is not None:
-        import surfel_io
-        from surfel_mesh import TriangleMesh
-        mesh = TriangleMesh(*(torch.from_numpy(a).to(dev) for a in surfel_io.read_triangle_mesh(args.mesh)))
+        from surfel_mesh import read_mesh
+        mesh = read_mesh(args.mesh, dev)
     viewer = Viewer(args.ip, args.port, mesh=mesh, texture=texture)
     metrics = {"#": int(gaussians.get_opacity.shape[0])}
     try:

@@ -22,23 +22,16 @@ torch = pytest.importorskip("torch")
 
 import cull_oracle as O  # noqa: E402
 import cull_scenes as S  # noqa: E402
+import device_mesh  # noqa: E402
+from device_mesh import dev as _dev, to_device as _t  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 ZN, ZF, EPS = S.SCENE["znear"], S.SCENE["zfar"], S.SCENE["eps"]
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _mesh(v, t, c=None):
-    from surfel_mesh import TriangleMesh
-    return TriangleMesh(_t(v.astype(np.float32)), _t(t.astype(np.int32)), _t(c) if c is not None else torch.zeros((len(v), 3), device=_dev()))
+def _mesh(v, t, c=None):      # (a mesh without colours carries zeros here)
+    return device_mesh.mesh(v, t, np.zeros((len(v), 3), np.float32) if c is None else c)
 
 
 @pytest.fixture(scope="module")

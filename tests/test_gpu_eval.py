@@ -14,6 +14,8 @@ torch = pytest.importorskip("torch")
 
 import eval_oracle as O  # noqa: E402
 import eval_scenes as S  # noqa: E402
+import device_mesh  # noqa: E402
+from device_mesh import dev as _dev, to_device as _t  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # Bar on the same-seed |ours - reference| of a mean on the fixture.  The first bar is the reference against itself: its seed-to-seed
@@ -23,17 +25,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAME_SEED_BAR = 7e-6
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _mesh(v, t):
-    from surfel_mesh import TriangleMesh
-    return TriangleMesh(_t(v.astype(np.float32)), _t(t.astype(np.int32)), torch.zeros((len(v), 3), device=_dev()))
+def _mesh(v, t):      # (zeros for colours)
+    return device_mesh.mesh(v, t, np.zeros((len(v), 3), np.float32))
 
 
 @pytest.fixture(scope="module")

@@ -18,23 +18,11 @@ import cull_oracle as O  # noqa: E402
 import cull_scenes as S  # noqa: E402
 import meshview_oracle as M  # noqa: E402
 import view_scenes as VS  # noqa: E402
+from device_mesh import dev as _dev, mesh as _mesh, to_device as _t  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ZN, ZF = S.SCENE["znear"], S.SCENE["zfar"]
 SHADE_VIEWS = (0, 11, 23, 24)      # an ordinary view at either end of the arc's first half, the filler's view, the view that sees nothing
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _mesh(v, t, c=None):
-    from surfel_mesh import TriangleMesh
-    return TriangleMesh(_t(v.astype(np.float32)), _t(t.astype(np.int32)), _t(c.astype(np.float32)) if c is not None else None)
 
 
 def _keys(ref, ssaa=1, views=None, **kw):

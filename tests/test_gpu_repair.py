@@ -18,22 +18,10 @@ torch = pytest.importorskip("torch")
 import repair_oracle as O  # noqa: E402
 import repair_scenes as R  # noqa: E402
 import test_repair_cpu as TC  # noqa: E402  (the restatement's results, computed once for both files)
+from device_mesh import dev as _dev, mesh as _mesh, to_device as _t  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = TC.CASES
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _mesh(v, t, c=None):
-    from surfel_mesh import TriangleMesh
-    return TriangleMesh(_t(np.asarray(v, np.float32)), _t(np.asarray(t, np.int32)), _t(np.asarray(c, np.float32)) if c is not None else None)
 
 
 def _bits(x):

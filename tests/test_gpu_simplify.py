@@ -14,22 +14,10 @@ torch = pytest.importorskip("torch")
 
 import simplify_oracle as O  # noqa: E402
 import simplify_scenes as S  # noqa: E402
+from device_mesh import dev as _dev, mesh as _mesh, to_device as _t  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAT_KEYS = ("clusters", "vertices", "triangles", "dropped", "collapsed", "duplicates")
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _mesh(v, t, c=None):
-    from surfel_mesh import TriangleMesh
-    return TriangleMesh(_t(np.asarray(v, np.float32)), _t(np.asarray(t, np.int32)), _t(np.asarray(c, np.float32)) if c is not None else None)
 
 
 def _bits(x):

@@ -13,6 +13,8 @@ torch = pytest.importorskip("torch")
 
 import tnt_oracle as O  # noqa: E402
 import tnt_scenes as S  # noqa: E402
+import device_mesh  # noqa: E402
+from device_mesh import dev as _dev, to_device as _t  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAU = S.FIXTURE["tau"]
@@ -23,17 +25,8 @@ MEASURED_DISPLACEMENT = 5.9e-7
 DISPLACEMENT_BAR = 10 * MEASURED_DISPLACEMENT
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _mesh(v, t):
-    from surfel_mesh import TriangleMesh
-    return TriangleMesh(_t(v.astype(np.float32)), _t(t.astype(np.int32)), torch.zeros((len(v), 3), device=_dev()))
+def _mesh(v, t):      # (zeros for colours)
+    return device_mesh.mesh(v, t, np.zeros((len(v), 3), np.float32))
 
 
 @pytest.fixture(scope="module")
