@@ -61,7 +61,7 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          # (tests/repair_oracle.py) and the repaired vertices come out bit for bit
          "mesh_repair.hip": ["-ffp-contract=off"]}
 HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
-           os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", "mesh_mc.h", "block_ops.h", "side_util.h", "mesh_topology.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
+           os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", "mesh_mc.h", "block_ops.h", "side_util.h", "carve.h", "mesh_topology.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
            os.path.join("..", "..", "include", "surfel_mesh_unbounded.h"), os.path.join("..", "..", "include", "surfel_eval.h"),
            os.path.join("..", "..", "include", "surfel_eval_tnt.h"), os.path.join("..", "..", "include", "surfel_metrics.h"),
            os.path.join("..", "..", "include", "surfel_scene.h"), "vis_turbo_table.h", os.path.join("..", "..", "include", "surfel_vis.h"),

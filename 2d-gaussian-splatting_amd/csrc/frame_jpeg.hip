@@ -23,6 +23,7 @@
 
 #include "../../include/surfel_jpeg.h"
 #include "block_ops.h"
+#include "carve.h"
 #include "jpeg_tables.h"
 #include "side_util.h"
 
@@ -296,9 +297,7 @@ __global__ void __launch_bounds__(JT) jpeg_stuff_kernel(int nrows, const RowInfo
 namespace {
 
 struct JpegGeometry {
-    int64_t rows, mcus, nblocks, row_bytes;
-    int64_t coef_bytes, rowbuf_bytes, bits_bytes, info_bytes;
-    int64_t scratch() const { return coef_bytes + rowbuf_bytes + bits_bytes + info_bytes; }
+    int64_t rows, mcus, nblocks, row_bytes, rowbuf_bytes;
 };
 
 inline JpegGeometry jpeg_geometry(int H, int W) {
@@ -307,12 +306,23 @@ inline JpegGeometry jpeg_geometry(int H, int W) {
     g.mcus = (W + 15) / 16;
     g.nblocks = g.rows * g.mcus * 6;
     g.row_bytes = g.mcus * MCU_BYTES;                 // a multiple of 16
-    g.coef_bytes = g.nblocks * 128;
     g.rowbuf_bytes = g.rows * g.row_bytes;
-    g.bits_bytes = (g.nblocks * 4 + 15) / 16 * 16;
-    g.info_bytes = g.rows * (int64_t)sizeof(RowInfo);
     return g;
 }
+
+struct JpegScratch {      // the scratch, described once: base == nullptr measures, the caller's pointer hands out the arrays
+    int16_t* coef; uint32_t *rowbuf, *blockbits; RowInfo* rows;
+    int64_t total;
+    static JpegScratch carve(void* base, const JpegGeometry& g) {
+        Carver c(base, 16); JpegScratch p;
+        p.coef = c.take<int16_t>((size_t)g.nblocks * 64);
+        p.rowbuf = c.take<uint32_t>((size_t)g.rowbuf_bytes / 4);
+        p.blockbits = c.take<uint32_t>((size_t)g.nblocks);
+        p.rows = c.take<RowInfo>((size_t)g.rows);
+        p.total = (int64_t)c.size();
+        return p;
+    }
+};
 
 inline int jpeg_size_check(const char* who, int H, int W) {
     char msg[96];
@@ -372,7 +382,7 @@ int64_t surfel_jpeg_capacity(int H, int W) {
 
 int64_t surfel_jpeg_scratch_bytes(int H, int W) {
     if (const int rc = jpeg_size_check("jpeg_scratch_bytes", H, W)) return rc;
-    return jpeg_geometry(H, W).scratch();
+    return JpegScratch::carve(nullptr, jpeg_geometry(H, W)).total;
 }
 
 int surfel_jpeg_encode(int H, int W, const uint8_t* rgb, int quality, uint8_t* dst, int64_t capacity, int64_t* size, void* scratch,
@@ -383,28 +393,24 @@ int surfel_jpeg_encode(int H, int W, const uint8_t* rgb, int quality, uint8_t* d
         return api_fail(SURFEL_E_INVALID, "jpeg_encode: bad arguments (a NULL pointer, or size / scratch not 8-byte aligned)");
     const JpegGeometry g = jpeg_geometry(H, W);
     if (capacity < surfel_jpeg_capacity(H, W)) return api_fail(SURFEL_E_INVALID, "jpeg_encode: capacity is below surfel_jpeg_capacity(H, W)");
-    if (scratch_bytes < g.scratch()) return api_fail(SURFEL_E_INVALID, "jpeg_encode: scratch holds fewer than surfel_jpeg_scratch_bytes(H, W)");
+    const JpegScratch p = JpegScratch::carve(scratch, g);
+    if (scratch_bytes < p.total) return api_fail(SURFEL_E_INVALID, "jpeg_encode: scratch holds fewer than surfel_jpeg_scratch_bytes(H, W)");
     JpegQuant qt;
     JpegHeader hdr = {};
     jpeg_scaled_tables(quality, &qt);
     if (jpeg_header(H, W, (int)g.mcus, qt, &hdr) != SURFEL_JPEG_HEADER_BYTES) return api_fail(SURFEL_E_INVALID, "jpeg_encode: header size");
-    uint8_t* base = static_cast<uint8_t*>(scratch);
-    int16_t* coef = reinterpret_cast<int16_t*>(base);
-    uint32_t* rowbuf = reinterpret_cast<uint32_t*>(base + g.coef_bytes);
-    uint32_t* blockbits = reinterpret_cast<uint32_t*>(base + g.coef_bytes + g.rowbuf_bytes);
-    RowInfo* rows = reinterpret_cast<RowInfo*>(base + g.coef_bytes + g.rowbuf_bytes + g.bits_bytes);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t row_words = g.row_bytes / 4;
     const unsigned wave_blocks = (unsigned)((g.nblocks + JT / 64 - 1) / (JT / 64));
-    const hipError_t e = hipMemsetAsync(rowbuf, 0, (size_t)g.rowbuf_bytes, s);
+    const hipError_t e = hipMemsetAsync(p.rowbuf, 0, (size_t)g.rowbuf_bytes, s);
     if (e != hipSuccess) return api_fail(SURFEL_E_HIP, "jpeg_encode: hipMemsetAsync", e);
-    hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)(g.rows * g.mcus)), dim3(JT_MCU), 0, s, H, W, (int)g.mcus, rgb, qt, coef);
-    hipLaunchKernelGGL(jpeg_block_bits_kernel, dim3(wave_blocks), dim3(JT), 0, s, g.nblocks, (int)g.mcus, coef, blockbits);
-    hipLaunchKernelGGL(jpeg_row_scan_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, (int)g.mcus, blockbits, rows, rowbuf, row_words);
-    hipLaunchKernelGGL(jpeg_emit_kernel, dim3(wave_blocks), dim3(JT), 0, s, g.nblocks, (int)g.mcus, coef, blockbits, rowbuf, row_words);
-    hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, rows, rowbuf, row_words);
-    hipLaunchKernelGGL(jpeg_finish_kernel, dim3(1), dim3(JT), 0, s, (int)g.rows, rows, hdr, dst, size);
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, (int)g.rows, rows, rowbuf, row_words, dst + SURFEL_JPEG_HEADER_BYTES);
+    hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)(g.rows * g.mcus)), dim3(JT_MCU), 0, s, H, W, (int)g.mcus, rgb, qt, p.coef);
+    hipLaunchKernelGGL(jpeg_block_bits_kernel, dim3(wave_blocks), dim3(JT), 0, s, g.nblocks, (int)g.mcus, p.coef, p.blockbits);
+    hipLaunchKernelGGL(jpeg_row_scan_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, (int)g.mcus, p.blockbits, p.rows, p.rowbuf, row_words);
+    hipLaunchKernelGGL(jpeg_emit_kernel, dim3(wave_blocks), dim3(JT), 0, s, g.nblocks, (int)g.mcus, p.coef, p.blockbits, p.rowbuf, row_words);
+    hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, p.rows, p.rowbuf, row_words);
+    hipLaunchKernelGGL(jpeg_finish_kernel, dim3(1), dim3(JT), 0, s, (int)g.rows, p.rows, hdr, dst, size);
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)g.rows), dim3(JT), 0, s, (int)g.rows, p.rows, p.rowbuf, row_words, dst + SURFEL_JPEG_HEADER_BYTES);
     return launched("jpeg_encode kernels");
 }
 

@@ -21,6 +21,7 @@
 
 #include "../../include/surfel_png.h"
 #include "block_ops.h"
+#include "carve.h"
 #include "side_util.h"
 
 namespace surfel {
@@ -549,17 +550,14 @@ __global__ void __launch_bounds__(PF) png_finish_kernel(PngShape sh, const Strip
 
 namespace {
 
-inline int64_t pad16(int64_t v) { return (v + 15) / 16 * 16; }
+inline int64_t stripe_cap(int64_t L) { return (15 * L + SURFEL_PNG_STRIPE_EXTRA_BITS + 31) / 32 * 4; }
 
 struct PngGeometry {
     PngShape sh;
-    int64_t N, cap_last;
-    int64_t stream_bytes, tok_bytes, rowsum_bytes, hist_bytes, table_bytes, info_bytes, meta_bytes, bit_bytes;
-    int64_t scratch() const { return stream_bytes + tok_bytes + rowsum_bytes + hist_bytes + table_bytes + info_bytes + meta_bytes + bit_bytes; }
+    int64_t N;              // bytes of the filtered stream
+    int64_t bit_bytes;      // bytes of all stripes' bit buffers (a multiple of 4)
     int64_t capacity() const { return SURFEL_PNG_FRONT_BYTES + bit_bytes + 20; }
 };
-
-inline int64_t stripe_cap(int64_t L) { return (15 * L + SURFEL_PNG_STRIPE_EXTRA_BITS + 31) / 32 * 4; }
 
 inline PngGeometry png_geometry(int H, int W, int C) {
     PngGeometry g;
@@ -570,17 +568,28 @@ inline PngGeometry png_geometry(int H, int W, int C) {
     sh.stripes = (H + sh.rps - 1) / sh.rps;
     sh.cap_full = stripe_cap((int64_t)sh.rps * sh.row);
     g.N = (int64_t)H * sh.row;
-    g.cap_last = stripe_cap((int64_t)(H - (sh.stripes - 1) * sh.rps) * sh.row);
-    g.stream_bytes = pad16(g.N);
-    g.tok_bytes = pad16(2 * g.N);
-    g.rowsum_bytes = pad16(8 * (int64_t)H);
-    g.hist_bytes = (int64_t)sh.stripes * NSYM_PAD * 4;
-    g.table_bytes = (int64_t)sh.stripes * NSYM_PAD * 4;
-    g.info_bytes = (int64_t)sh.stripes * (int64_t)sizeof(StripeInfo);
-    g.meta_bytes = 16;
-    g.bit_bytes = (sh.stripes - 1) * sh.cap_full + g.cap_last;      // (multiples of 4; the scratch is padded below)
+    g.bit_bytes = (sh.stripes - 1) * sh.cap_full + stripe_cap((int64_t)(H - (sh.stripes - 1) * sh.rps) * sh.row);
     return g;
 }
+
+struct PngScratch {      // the scratch, described once: base == nullptr measures, the caller's pointer hands out the arrays
+    uint8_t* stream; uint16_t* tok; uint32_t *rowsum, *hist, *tables; StripeInfo* info; PngMeta* meta; uint32_t* bitbuf;
+    int64_t total;
+    static PngScratch carve(void* base, const PngGeometry& g) {
+        Carver c(base, 16); PngScratch p;
+        const size_t S = (size_t)g.sh.stripes;
+        p.stream = c.take<uint8_t>((size_t)g.N);
+        p.tok = c.take<uint16_t>((size_t)g.N);
+        p.rowsum = c.take<uint32_t>(2 * (size_t)g.sh.H);
+        p.hist = c.take<uint32_t>(S * NSYM_PAD);
+        p.tables = c.take<uint32_t>(S * NSYM_PAD);
+        p.info = c.take<StripeInfo>(S);
+        p.meta = c.take<PngMeta>(1);
+        p.bitbuf = c.take<uint32_t>((size_t)g.bit_bytes / 4);
+        p.total = (int64_t)c.size();
+        return p;
+    }
+};
 
 inline int png_size_check(const char* who, int H, int W, int C) {
     char msg[160];
@@ -623,7 +632,7 @@ int64_t surfel_png_capacity(int H, int W, int C) {
 
 int64_t surfel_png_scratch_bytes(int H, int W, int C) {
     if (const int rc = png_size_check("png_scratch_bytes", H, W, C)) return rc;
-    return pad16(png_geometry(H, W, C).scratch());
+    return PngScratch::carve(nullptr, png_geometry(H, W, C)).total;
 }
 
 int surfel_png_encode(int H, int W, int C, const uint8_t* pix, uint8_t* dst, int64_t capacity, int64_t* size, void* scratch,
@@ -633,7 +642,8 @@ int surfel_png_encode(int H, int W, int C, const uint8_t* pix, uint8_t* dst, int
         return api_fail(SURFEL_E_INVALID, "png_encode: bad arguments (a NULL pointer, or size / scratch not 8-byte aligned)");
     const PngGeometry g = png_geometry(H, W, C);
     if (capacity < g.capacity()) return api_fail(SURFEL_E_INVALID, "png_encode: capacity is below surfel_png_capacity(H, W, C)");
-    if (scratch_bytes < pad16(g.scratch())) return api_fail(SURFEL_E_INVALID, "png_encode: scratch holds fewer than surfel_png_scratch_bytes(H, W, C)");
+    const PngScratch p = PngScratch::carve(scratch, g);
+    if (scratch_bytes < p.total) return api_fail(SURFEL_E_INVALID, "png_encode: scratch holds fewer than surfel_png_scratch_bytes(H, W, C)");
     PngFront front = {};
     const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
     memcpy(front.b, sig, 8);
@@ -646,26 +656,17 @@ int surfel_png_encode(int H, int W, int C, const uint8_t* pix, uint8_t* dst, int
     memcpy(front.b + 37, "IDAT", 4);
     front.b[41] = 0x78, front.b[42] = 0x01;             // zlib: deflate, 32 KiB window, no preset dictionary, fastest level
     const uint32_t head_crc = host_crc32(front.b + 37, 6);
-    uint8_t* base = static_cast<uint8_t*>(scratch);
-    uint8_t* filtered_stream = base;
-    uint16_t* tok = reinterpret_cast<uint16_t*>(base + g.stream_bytes);
-    uint32_t* rowsum = reinterpret_cast<uint32_t*>(base + g.stream_bytes + g.tok_bytes);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(rowsum) + g.rowsum_bytes);
-    uint32_t* tables = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(hist) + g.hist_bytes);
-    StripeInfo* info = reinterpret_cast<StripeInfo*>(reinterpret_cast<uint8_t*>(tables) + g.table_bytes);
-    PngMeta* meta = reinterpret_cast<PngMeta*>(reinterpret_cast<uint8_t*>(info) + g.info_bytes);
-    uint32_t* bitbuf = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(meta) + g.meta_bytes);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned S = (unsigned)g.sh.stripes;
-    const hipError_t e = hipMemsetAsync(bitbuf, 0, (size_t)g.bit_bytes, s);
+    const hipError_t e = hipMemsetAsync(p.bitbuf, 0, (size_t)g.bit_bytes, s);
     if (e != hipSuccess) return api_fail(SURFEL_E_HIP, "png_encode: hipMemsetAsync", e);
-    hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)H), dim3(PF), 0, s, g.sh, pix, filtered_stream, rowsum);
-    hipLaunchKernelGGL(png_token_kernel, dim3(S), dim3(PT), 0, s, g.sh, filtered_stream, tok, hist);
-    hipLaunchKernelGGL(png_codes_kernel, dim3(S), dim3(64), 0, s, g.sh, hist, tables, info, bitbuf);
-    hipLaunchKernelGGL(png_emit_kernel, dim3(S), dim3(PT), 0, s, g.sh, tok, tables, info, bitbuf);
-    hipLaunchKernelGGL(png_layout_kernel, dim3(1), dim3(PF), 0, s, g.sh, rowsum, info, meta);
-    hipLaunchKernelGGL(png_compact_kernel, dim3(S), dim3(PF), 0, s, g.sh, info, bitbuf, dst + SURFEL_PNG_FRONT_BYTES);
-    hipLaunchKernelGGL(png_finish_kernel, dim3(1), dim3(PF), 0, s, g.sh, info, meta, front, head_crc, dst, size);
+    hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)H), dim3(PF), 0, s, g.sh, pix, p.stream, p.rowsum);
+    hipLaunchKernelGGL(png_token_kernel, dim3(S), dim3(PT), 0, s, g.sh, p.stream, p.tok, p.hist);
+    hipLaunchKernelGGL(png_codes_kernel, dim3(S), dim3(64), 0, s, g.sh, p.hist, p.tables, p.info, p.bitbuf);
+    hipLaunchKernelGGL(png_emit_kernel, dim3(S), dim3(PT), 0, s, g.sh, p.tok, p.tables, p.info, p.bitbuf);
+    hipLaunchKernelGGL(png_layout_kernel, dim3(1), dim3(PF), 0, s, g.sh, p.rowsum, p.info, p.meta);
+    hipLaunchKernelGGL(png_compact_kernel, dim3(S), dim3(PF), 0, s, g.sh, p.info, p.bitbuf, dst + SURFEL_PNG_FRONT_BYTES);
+    hipLaunchKernelGGL(png_finish_kernel, dim3(1), dim3(PF), 0, s, g.sh, p.info, p.meta, front, head_crc, dst, size);
     return launched("png_encode kernels");
 }
 

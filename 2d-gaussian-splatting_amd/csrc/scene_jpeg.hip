@@ -21,6 +21,7 @@
 
 #include "../../include/surfel_jpegdec.h"
 #include "block_ops.h"
+#include "carve.h"
 #include "side_util.h"
 
 namespace surfel {
@@ -71,40 +72,37 @@ struct JpegGeom {
     int64_t plane_off[3];
 };
 
-inline int64_t pad16(int64_t v) { return (v + 15) / 16 * 16; }
+inline int64_t clean_bytes(const JpegGeom& g) { return (int64_t)align_up((size_t)g.n + 16, 16); }      // zeroed before every decode
 
-struct Layout {      // byte offsets into the scratch
-    int64_t ctrl, tabs, keep, rst, scan, clean, istart, nsub, subs, state0, state1, lastin, nblk, first, coef, dc, planes, total;
+struct JpegDecScratch {      // the scratch, described once: base == nullptr measures, the caller's pointer hands out the arrays
+    uint32_t* ctrl; HuffTables* tabs; uint32_t *keep, *rst, *scan; uint8_t* clean; uint32_t *istart, *nsub; uint4* subs;
+    uint2* state[2]; uint2* lastin; uint32_t *nblk, *first; int16_t* coef; uint32_t* dc; uint8_t* planes;
+    int64_t total;
+    static JpegDecScratch carve(void* base, const JpegGeom& g) {
+        Carver c(base, 16); JpegDecScratch p;
+        const size_t n1 = (size_t)g.n + 1, ns = g.ns_max, ns1 = ns + 1, nb1 = (size_t)g.nblocks + 1, e1 = (size_t)g.nint + 1;
+        const size_t a = n1 > ns1 ? n1 : ns1, b = nb1 > e1 ? nb1 : e1, longest = a > b ? a : b;      // the scans share one scratch
+        p.ctrl = c.take<uint32_t>(CTRL_WORDS);
+        p.tabs = c.take<HuffTables>(1);
+        p.keep = c.take<uint32_t>(n1);
+        p.rst = c.take<uint32_t>(n1);
+        p.scan = c.take<uint32_t>((size_t)scan_scratch_u32((int64_t)longest));
+        p.clean = c.take<uint8_t>((size_t)clean_bytes(g));
+        p.istart = c.take<uint32_t>(e1);
+        p.nsub = c.take<uint32_t>(e1);
+        p.subs = c.take<uint4>(ns);
+        p.state[0] = c.take<uint2>(ns);
+        p.state[1] = c.take<uint2>(ns);
+        p.lastin = c.take<uint2>(ns);
+        p.nblk = c.take<uint32_t>(ns1);
+        p.first = c.take<uint32_t>(ns1);
+        p.coef = c.take<int16_t>(64 * (size_t)g.nblocks);
+        p.dc = c.take<uint32_t>(nb1);
+        p.planes = c.take<uint8_t>((size_t)(g.plane_off[g.ncomp - 1] + (int64_t)g.plane_w[g.ncomp - 1] * g.plane_h[g.ncomp - 1]));
+        p.total = (int64_t)c.size();
+        return p;
+    }
 };
-
-inline Layout layout(const JpegGeom& g) {
-    Layout L;
-    int64_t o = 0;
-    auto take_bytes = [&](int64_t bytes) { const int64_t at = o; o += pad16(bytes); return at; };
-    const int64_t n1 = (int64_t)g.n + 1, ns1 = (int64_t)g.ns_max + 1, nb1 = (int64_t)g.nblocks + 1, e1 = (int64_t)g.nint + 1;
-    int64_t longest = n1 > ns1 ? n1 : ns1;
-    if (nb1 > longest) longest = nb1;
-    if (e1 > longest) longest = e1;
-    L.ctrl = take_bytes(4 * CTRL_WORDS);
-    L.tabs = take_bytes(sizeof(HuffTables));
-    L.keep = take_bytes(4 * n1);
-    L.rst = take_bytes(4 * n1);
-    L.scan = take_bytes(4 * scan_scratch_u32(longest));
-    L.clean = take_bytes((int64_t)g.n + 16);
-    L.istart = take_bytes(4 * e1);
-    L.nsub = take_bytes(4 * e1);
-    L.subs = take_bytes(16 * (int64_t)g.ns_max);
-    L.state0 = take_bytes(8 * (int64_t)g.ns_max);
-    L.state1 = take_bytes(8 * (int64_t)g.ns_max);
-    L.lastin = take_bytes(8 * (int64_t)g.ns_max);
-    L.nblk = take_bytes(4 * ns1);
-    L.first = take_bytes(4 * ns1);
-    L.coef = take_bytes(128 * (int64_t)g.nblocks);
-    L.dc = take_bytes(4 * nb1);
-    L.planes = take_bytes(g.plane_off[g.ncomp - 1] + (int64_t)g.plane_w[g.ncomp - 1] * g.plane_h[g.ncomp - 1]);
-    L.total = o;
-    return L;
-}
 
 // ------------------------------------------------------------------------------------------------ 1. the clean stream
 __global__ void __launch_bounds__(JT) jpegdec_init_kernel(JpegGeom g, uint32_t* __restrict__ ctrl) {
@@ -501,7 +499,7 @@ inline int geometry(const char* who, const surfel_jpegdec_desc* d, int subseq_bi
         g.tq[c] = d->tq[c], g.td[c] = d->td[c], g.ta[c] = d->ta[c];
         g.plane_w[c] = g.mcux * 8 * (c == 0 ? g.hs : 1), g.plane_h[c] = g.mcuy * 8 * (c == 0 ? g.vs : 1);
         g.plane_off[c] = off;
-        off += pad16((int64_t)g.plane_w[c] * g.plane_h[c]);
+        off += (int64_t)align_up((size_t)g.plane_w[c] * g.plane_h[c], 16);
         g.dc_base[c] = c == 0 ? 0 : g.nmcu * g.ny + (c - 1) * g.nmcu;
     }
     *out = g;
@@ -518,7 +516,7 @@ extern "C" {
 int64_t surfel_jpegdec_scratch_bytes(const surfel_jpegdec_desc* desc, int subseq_bits) {
     JpegGeom g;
     if (const int rc = geometry("jpegdec_scratch_bytes", desc, subseq_bits, 1, &g)) return rc;
-    return layout(g).total;
+    return JpegDecScratch::carve(nullptr, g).total;
 }
 
 int surfel_jpegdec_decode(const surfel_jpegdec_desc* desc, const uint8_t* file, int64_t file_bytes, uint8_t* out, void* scratch,
@@ -528,75 +526,58 @@ int surfel_jpegdec_decode(const surfel_jpegdec_desc* desc, const uint8_t* file, 
     if (!file || !out || !scratch || !status || (reinterpret_cast<uintptr_t>(scratch) & 15) || (reinterpret_cast<uintptr_t>(status) & 3))
         return api_fail(SURFEL_E_INVALID, "jpegdec_decode: bad arguments (a NULL pointer, scratch not 16-byte or status not 4-byte aligned)");
     if (desc->ecs_offset + desc->ecs_bytes > file_bytes) return api_fail(SURFEL_E_INVALID, "jpegdec_decode: the entropy-coded segment ends behind the file");
-    const Layout L = layout(g);
-    if (scratch_bytes < L.total) return api_fail(SURFEL_E_INVALID, "jpegdec_decode: scratch holds fewer than surfel_jpegdec_scratch_bytes(desc, subseq_bits)");
-    uint8_t* base = static_cast<uint8_t*>(scratch);
-    uint32_t* ctrl = reinterpret_cast<uint32_t*>(base + L.ctrl);
-    HuffTables* tabs = reinterpret_cast<HuffTables*>(base + L.tabs);
-    uint32_t* keep = reinterpret_cast<uint32_t*>(base + L.keep);
-    uint32_t* rst = reinterpret_cast<uint32_t*>(base + L.rst);
-    uint32_t* scan = reinterpret_cast<uint32_t*>(base + L.scan);
-    uint8_t* clean = base + L.clean;
-    uint32_t* istart = reinterpret_cast<uint32_t*>(base + L.istart);
-    uint32_t* nsub = reinterpret_cast<uint32_t*>(base + L.nsub);
-    uint4* subs = reinterpret_cast<uint4*>(base + L.subs);
-    uint2* state[2] = {reinterpret_cast<uint2*>(base + L.state0), reinterpret_cast<uint2*>(base + L.state1)};
-    uint2* lastin = reinterpret_cast<uint2*>(base + L.lastin);
-    uint32_t* nblk = reinterpret_cast<uint32_t*>(base + L.nblk);
-    uint32_t* first = reinterpret_cast<uint32_t*>(base + L.first);
-    int16_t* coef = reinterpret_cast<int16_t*>(base + L.coef);
-    uint32_t* dc = reinterpret_cast<uint32_t*>(base + L.dc);
-    uint8_t* planes = base + L.planes;
+    const JpegDecScratch p = JpegDecScratch::carve(scratch, g);
+    if (scratch_bytes < p.total) return api_fail(SURFEL_E_INVALID, "jpegdec_decode: scratch holds fewer than surfel_jpegdec_scratch_bytes(desc, subseq_bits)");
     const uint8_t* ecs = file + desc->ecs_offset;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n1 = (int64_t)g.n + 1, ns1 = (int64_t)g.ns_max + 1;
     const unsigned lanes = blocks_for(g.ns_max, JT);
 
     if (stages & SURFEL_JPEGDEC_CLEAN) {
-        hipError_t e = hipMemsetAsync(clean, 0, (size_t)pad16((int64_t)g.n + 16), s);
-        if (e == hipSuccess) e = hipMemsetAsync(istart, 0, (size_t)(4 * (g.nint + 1)), s);
+        hipError_t e = hipMemsetAsync(p.clean, 0, (size_t)clean_bytes(g), s);
+        if (e == hipSuccess) e = hipMemsetAsync(p.istart, 0, (size_t)(4 * (g.nint + 1)), s);
         if (e != hipSuccess) return api_fail(SURFEL_E_HIP, "jpegdec_decode: hipMemsetAsync", e);
-        hipLaunchKernelGGL(jpegdec_init_kernel, dim3(1), dim3(JT), 0, s, g, ctrl);
-        hipLaunchKernelGGL(jpegdec_classify_kernel, dim3(blocks_for(n1, JT)), dim3(JT), 0, s, g, ecs, keep, rst, ctrl);
-        scan_u32(keep, n1, scan, s);
-        scan_u32(rst, n1, scan, s);
-        hipLaunchKernelGGL(jpegdec_compact_kernel, dim3(blocks_for(n1, JT)), dim3(JT), 0, s, g, ecs, keep, rst, clean, istart, ctrl);
-        hipLaunchKernelGGL(jpegdec_nsub_kernel, dim3(blocks_for(g.nint + 1, JT)), dim3(JT), 0, s, g, istart, nsub, ctrl);
-        scan_u32(nsub, g.nint + 1, scan, s);
-        hipLaunchKernelGGL(jpegdec_subs_kernel, dim3(lanes), dim3(JT), 0, s, g, istart, nsub, subs, ctrl);
+        hipLaunchKernelGGL(jpegdec_init_kernel, dim3(1), dim3(JT), 0, s, g, p.ctrl);
+        hipLaunchKernelGGL(jpegdec_classify_kernel, dim3(blocks_for(n1, JT)), dim3(JT), 0, s, g, ecs, p.keep, p.rst, p.ctrl);
+        scan_u32(p.keep, n1, p.scan, s);
+        scan_u32(p.rst, n1, p.scan, s);
+        hipLaunchKernelGGL(jpegdec_compact_kernel, dim3(blocks_for(n1, JT)), dim3(JT), 0, s, g, ecs, p.keep, p.rst, p.clean, p.istart, p.ctrl);
+        hipLaunchKernelGGL(jpegdec_nsub_kernel, dim3(blocks_for(g.nint + 1, JT)), dim3(JT), 0, s, g, p.istart, p.nsub, p.ctrl);
+        scan_u32(p.nsub, g.nint + 1, p.scan, s);
+        hipLaunchKernelGGL(jpegdec_subs_kernel, dim3(lanes), dim3(JT), 0, s, g, p.istart, p.nsub, p.subs, p.ctrl);
         HuffSpec spec;
         memcpy(spec.bits, desc->bits, sizeof spec.bits);
         memcpy(spec.huffval, desc->huffval, sizeof spec.huffval);
-        hipLaunchKernelGGL(jpegdec_tables_kernel, dim3(1), dim3(64), 0, s, spec, tabs);
+        hipLaunchKernelGGL(jpegdec_tables_kernel, dim3(1), dim3(64), 0, s, spec, p.tabs);
     }
     if (stages & SURFEL_JPEGDEC_HUFFMAN) {
-        hipError_t e = hipMemsetAsync(nblk, 0, (size_t)(4 * ns1), s);
-        if (e == hipSuccess) e = hipMemsetAsync(ctrl + C_CHANGED, 0, 4 * SURFEL_JPEGDEC_MAX_ROUNDS, s);
+        hipError_t e = hipMemsetAsync(p.nblk, 0, (size_t)(4 * ns1), s);
+        if (e == hipSuccess) e = hipMemsetAsync(p.ctrl + C_CHANGED, 0, 4 * SURFEL_JPEGDEC_MAX_ROUNDS, s);
         if (e != hipSuccess) return api_fail(SURFEL_E_HIP, "jpegdec_decode: hipMemsetAsync", e);
         for (int r = 0; r < max_rounds; r++)
-            hipLaunchKernelGGL(jpegdec_huffman_kernel, dim3(lanes), dim3(JT), 0, s, g, r, reinterpret_cast<const uint32_t*>(clean), subs, tabs,
-                               state[(r + 1) & 1], state[r & 1], lastin, nblk, ctrl);
+            hipLaunchKernelGGL(jpegdec_huffman_kernel, dim3(lanes), dim3(JT), 0, s, g, r, reinterpret_cast<const uint32_t*>(p.clean), p.subs, p.tabs,
+                               p.state[(r + 1) & 1], p.state[r & 1], p.lastin, p.nblk, p.ctrl);
     }
     if (stages & SURFEL_JPEGDEC_WRITE) {
-        hipError_t e = hipMemsetAsync(coef, 0, (size_t)(128 * (int64_t)g.nblocks), s);
-        if (e == hipSuccess) e = hipMemcpyAsync(first, nblk, (size_t)(4 * ns1), hipMemcpyDeviceToDevice, s);
+        hipError_t e = hipMemsetAsync(p.coef, 0, (size_t)(128 * (int64_t)g.nblocks), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(p.first, p.nblk, (size_t)(4 * ns1), hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return api_fail(SURFEL_E_HIP, "jpegdec_decode: hipMemsetAsync / hipMemcpyAsync", e);
-        scan_u32(first, ns1, scan, s);
-        hipLaunchKernelGGL(jpegdec_write_kernel, dim3(lanes), dim3(JT), 0, s, g, reinterpret_cast<const uint32_t*>(clean), subs, tabs,
-                           state[(max_rounds - 1) & 1], first, coef, ctrl);
+        scan_u32(p.first, ns1, p.scan, s);
+        hipLaunchKernelGGL(jpegdec_write_kernel, dim3(lanes), dim3(JT), 0, s, g, reinterpret_cast<const uint32_t*>(p.clean), p.subs, p.tabs,
+                           p.state[(max_rounds - 1) & 1], p.first, p.coef, p.ctrl);
     }
     if (stages & SURFEL_JPEGDEC_DC) {
-        hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(blocks_for(g.nblocks + 1, JT)), dim3(JT), 0, s, g, coef, dc);
-        scan_u32(dc, (int64_t)g.nblocks + 1, scan, s);
+        hipLaunchKernelGGL(jpegdec_dc_kernel, dim3(blocks_for(g.nblocks + 1, JT)), dim3(JT), 0, s, g, p.coef, p.dc);
+        scan_u32(p.dc, (int64_t)g.nblocks + 1, p.scan, s);
     }
     if (stages & SURFEL_JPEGDEC_IDCT) {
         QuantTables qt;
         memcpy(qt.q, desc->qt, sizeof qt.q);
-        hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(blocks_for(g.nblocks, JT / 8)), dim3(JT), 0, s, g, qt, coef, dc, planes);
+        hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(blocks_for(g.nblocks, JT / 8)), dim3(JT), 0, s, g, qt, p.coef, p.dc, p.planes);
     }
     if (stages & SURFEL_JPEGDEC_COLOUR) {
-        hipLaunchKernelGGL(jpegdec_colour_kernel, dim3(blocks_for((int64_t)g.W * g.H, JT)), dim3(JT), 0, s, g, planes, out);
-        hipLaunchKernelGGL(jpegdec_status_kernel, dim3(1), dim3(64), 0, s, g, ctrl, first, status);
+        hipLaunchKernelGGL(jpegdec_colour_kernel, dim3(blocks_for((int64_t)g.W * g.H, JT)), dim3(JT), 0, s, g, p.planes, out);
+        hipLaunchKernelGGL(jpegdec_status_kernel, dim3(1), dim3(64), 0, s, g, p.ctrl, p.first, status);
     }
     return launched("jpegdec_decode kernels");
 }

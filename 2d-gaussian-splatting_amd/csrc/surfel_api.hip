@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/surfel_debug.h"
+#include "carve.h"
 #include "surfel_common.h"
 #include "surfel_kernels.h"
 #include "train_kernels.h"
@@ -71,21 +72,6 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
         hipError_t _e = (expr);                                          \
         if (_e != hipSuccess) return fail(SURFEL_E_HIP, #expr, _e);      \
     } while (0)
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-// Bump carving of an opaque buffer; with base == nullptr it only measures.
-struct Carver {
-    char* base; size_t off = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    template <typename T> T* take(size_t count) {
-        off = align_up(off);
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-    size_t size() const { return align_up(off); }
-};
 
 struct GeomState {   // per-surfel state ("geomBuffer")
     float* rec; float* depths; uint32_t* tiles_touched; uint8_t* clamped;

@@ -130,10 +130,7 @@ def panel(mode, planes, out=None, scratch=None):
         raise ValueError("surfel_log.panel: mode %s takes [%d, H, W] planes, got %s" % (mode, need, tuple(planes.shape)))
     t = t.contiguous()
     H, W = int(t.shape[1]), int(t.shape[2])
-    if out is None:
-        out = torch.empty((H, W, 3), dtype=torch.uint8, device=t.device)
-    elif out.dtype != torch.uint8 or out.numel() != H * W * 3 or not out.is_contiguous():
-        raise ValueError("surfel_log.panel: out must be a contiguous uint8 tensor of %d elements" % (H * W * 3))
+    out = _n.uint8_buffer("surfel_log.panel", out, H * W * 3, t.device)
     if scratch is None:
         scratch = torch.empty(PANEL_SCRATCH_BYTES, dtype=torch.uint8, device=t.device)
     _n.call(t.device, "surfel_log_panel", MODES[mode], H, W, t, out, scratch, scratch.numel())
@@ -324,8 +321,7 @@ def report(trainer, writer, name, cams, first):
                 encoded.append((label, pix.shape, buf, size))
             values = []
             for label, shape, buf, size in encoded:      # (the launches of all panels are queued before the first wait)
-                png = buf[:int(size.item())].cpu().numpy().tobytes()
-                values.append(value_image("%s_view_%s/%s" % (name, cam.image_name, label), int(shape[0]), int(shape[1]), png))
+                values.append(value_image("%s_view_%s/%s" % (name, cam.image_name, label), int(shape[0]), int(shape[1]), _n.file_bytes(buf, size)))
             writer.add(it, values)
     ps, l1 = trainer.evaluate(cams)
     writer.add(it, [value_scalar(name + "/loss_viewpoint - l1_loss", l1), value_scalar(name + "/loss_viewpoint - psnr", ps)])

@@ -117,10 +117,7 @@ def shade(mesh, key, w2c, sample_intrinsics, H, W, ssaa=1, mode="shaded", normal
             raise ValueError("surfel_meshview: normals must be [V, 3], got %s" % list(normals.shape))
         normals = normals.detach().to(torch.float32).contiguous()
     n = key.shape[0]
-    if out is None:
-        out = torch.empty((n, int(H), int(W), 3), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.numel() != n * int(H) * int(W) * 3 or not out.is_contiguous():
-        raise ValueError("surfel_meshview: out must be a contiguous uint8 tensor of %d elements" % (n * int(H) * int(W) * 3))
+    out = _n.uint8_buffer("surfel_meshview", out, n * int(H) * int(W) * 3, dev)
     bg = [float(x) for x in background]
     _n.call(dev, "surfel_meshview_shade", verts.shape[0], tris.shape[0], verts, tris, cols, normals, n, w, k, k.shape[0], int(H), int(W), s, key,
             _KERNEL_MODE[mode], bg[0], bg[1], bg[2], out)

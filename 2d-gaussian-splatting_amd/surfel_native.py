@@ -6,7 +6,8 @@ already mapped by PyTorch-ROCm (same SONAME libamdhip64.so.7) is the one our lib
 here is plumbing only (device memory through its caching allocator, current stream).
 
 Adding a side module: check its tensors with device_tensor / rows below ("no CPU path: CPU tensors raise" is stated there, once),
-and take a mesh with surfel_mesh.mesh_arrays.
+and take a mesh with surfel_mesh.mesh_arrays; an `out=` buffer goes through uint8_buffer, a writer behind the renderer is built from
+surfel_frames.
 """
 import ctypes as C
 import math
@@ -446,11 +447,30 @@ def ptr(t):
 
 # ------------------------------------------------------------------------------------------------ argument checks of the side modules
 # (`who` is the calling module's name, the prefix of every message)
-def device_tensor(who, t, what):
-    """t, or "no CPU path: CPU tensors raise": RuntimeError for anything but a tensor on a HIP device"""
+def device_tensor(who, t, what=None):
+    """t, or "no CPU path: CPU tensors raise": RuntimeError for anything but a tensor on a HIP device.  what: the argument's name in
+    the message, for the modules that name it"""
     if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("%s: tensors must live on a HIP device (%s: got %s)" % (who, what, t.device if torch.is_tensor(t) else type(t).__name__))
+        got = t.device if torch.is_tensor(t) else type(t).__name__
+        raise RuntimeError("%s: tensors must live on a HIP device (%sgot %s)" % (who, "" if what is None else what + ": ", got))
     return t
+
+
+def uint8_buffer(who, t, n, device, what="out", at_least=False):
+    """The buffer for `n` output bytes: a new uint8 [n] on `device` when the caller supplied none (t is None), otherwise t — ValueError
+    unless it is a contiguous uint8 tensor of n elements (any shape) or, with at_least, a one-dimensional one of n elements or more
+    (the encoders' out and scratch)"""
+    if t is None:
+        return torch.empty(n, dtype=torch.uint8, device=device)
+    if t.dtype != torch.uint8 or not t.is_contiguous() or ((t.dim() != 1 or t.numel() < n) if at_least else t.numel() != n):
+        raise ValueError("%s: %s must be a contiguous uint8 tensor of %s%d elements" % (who, what, "at least " if at_least else "", n))
+    return t
+
+
+def file_bytes(buf, size):
+    """The file an encoder left on the device as bytes: waits for the int64 [1] device tensor `size`, then copies exactly that many
+    bytes of `buf`"""
+    return buf[:int(size.item())].cpu().numpy().tobytes()
 
 
 def rows(who, t, what, dtype, shape="[N, 3]"):

@@ -10,13 +10,13 @@ non-blocking copies and are encoded by worker threads while the renderer runs ah
 import copy
 import ctypes as C
 import os
-import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+import surfel_frames as _f
 import surfel_native as _n
 
 _n.load()
@@ -130,9 +130,7 @@ def generate_path(cameras, n_frames=240):
 
 # ------------------------------------------------------------------------------------------------ frame kernels
 def _planes(img):
-    if not torch.is_tensor(img) or not img.is_cuda:
-        raise RuntimeError("surfel_path: tensors must live on a HIP device (got %s)" % (img.device if torch.is_tensor(img) else type(img).__name__))
-    return img.detach().float().contiguous()
+    return _n.device_tensor("surfel_path", img).detach().float().contiguous()
 
 
 def quantize_u8(img, scale=1.0, bias=0.0, out=None):
@@ -142,10 +140,7 @@ def quantize_u8(img, scale=1.0, bias=0.0, out=None):
     if p.dim() == 2:
         p = p[None]
     Cn, H, W = (int(s) for s in p.shape)
-    if out is None:
-        out = torch.empty((H, W, Cn), dtype=torch.uint8, device=p.device)
-    elif out.dtype != torch.uint8 or out.numel() != H * W * Cn or not out.is_contiguous():
-        raise ValueError("quantize_u8: out must be a contiguous uint8 tensor of %d elements" % (H * W * Cn))
+    out = _n.uint8_buffer("quantize_u8", out, H * W * Cn, p.device)
     _n.call(p.device, "surfel_vis_quantize", Cn, H, W, p, float(scale), float(bias), out)
     return out.view(H, W, Cn)
 
@@ -214,10 +209,7 @@ def colorize_depth(depth, lo, hi, out=None):
     H, W = (int(s) for s in d.shape[-2:])
     if d.numel() != H * W:
         raise ValueError("colorize_depth: one depth plane expected, got %s" % (tuple(d.shape),))
-    if out is None:
-        out = torch.empty((H, W, 3), dtype=torch.uint8, device=d.device)
-    elif out.dtype != torch.uint8 or out.numel() != H * W * 3 or not out.is_contiguous():
-        raise ValueError("colorize_depth: out must be a contiguous uint8 tensor of %d elements" % (H * W * 3))
+    out = _n.uint8_buffer("colorize_depth", out, H * W * 3, d.device)
     _n.call(d.device, "surfel_vis_depth_turbo", H, W, d, float(lo), float(hi), out)
     return out.view(H, W, 3)
 
@@ -238,18 +230,17 @@ class FrameWriter:
         if png not in ("pillow", "device"):
             raise ValueError("FrameWriter: png must be 'pillow' or 'device', got %r" % (png,))
         self.png = png
-        self._device = None                     # png="device": made by the first device PNG
+        self._device = None                     # png="device": surfel_frames.EncodedStream, made by the first device PNG
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.ring = max(1, int(ring)) if ring is not None else 2 * self.workers
         self._pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="frame-writer")
-        self._free = threading.Semaphore(self.ring)
-        self._lock = threading.Lock()
-        self._buffers = [None] * self.ring      # uint8 host tensors, grown on demand
-        self._idle = list(range(self.ring))
+        self._ring = _f.SlotRing(self.ring)
+        self._idle = self._ring._idle           # (the ring's own list, under the name it had here)
+        self._buffers = [None] * self.ring      # uint8 host tensors of the Pillow path, grown on demand
         self._futures = []
-        self._error = None
-        self.wait_s = 0.0                       # time submit() spent waiting for a free buffer (encoders behind the renderer)
         self.frames = 0
+
+    wait_s = property(lambda self: self._ring.wait_s, doc="time submit() spent waiting for a free buffer (encoders behind the renderer)")
 
     def __enter__(self):
         return self
@@ -277,11 +268,7 @@ class FrameWriter:
             raise ValueError("FrameWriter.submit: uint8 [H, W, 1 or 3] or float32 [H, W] expected, got %s %s" % (t.dtype, tuple(t.shape)))
         if self._pool is None:
             raise RuntimeError("FrameWriter.submit after close()")
-        t0 = time.perf_counter()
-        self._free.acquire()
-        self.wait_s += time.perf_counter() - t0
-        with self._lock:
-            slot = self._idle.pop()
+        slot = self._ring.acquire()
         try:
             t = t.contiguous()
             if kind == "PNG" and self.png == "device" and t.is_cuda:
@@ -299,56 +286,27 @@ class FrameWriter:
             else:
                 host.copy_(t)
         except BaseException:
-            self._release(slot)
+            self._ring.release(slot)
             raise
         self.frames += 1
         self._futures.append(self._pool.submit(self._encode, slot, path, kind, host, event))
 
-    def _release(self, slot):
-        with self._lock:
-            self._idle.append(slot)
-        self._free.release()
-
     def _encode_device(self, slot, t):
         """the PNG file of a device frame into the slot's device buffer, its size into pinned memory; the event behind both"""
         import surfel_png
-        d = self._device
-        if d is None:
-            with torch.cuda.device(t.device):
-                d = self._device = dict(device=t.device, stream=torch.cuda.Stream(device=t.device), buffers=[None] * self.ring,
-                                        sizes=torch.zeros(self.ring, dtype=torch.int64, device=t.device),
-                                        host_size=torch.zeros(self.ring, dtype=torch.int64).pin_memory())
-        elif d["device"] != t.device:
-            raise ValueError("FrameWriter(png='device'): frames of one writer must live on one device (%s, then %s)" % (d["device"], t.device))
-        cap = surfel_png.capacity(*t.shape)
-        with torch.cuda.device(t.device):
-            if d["buffers"][slot] is None or d["buffers"][slot].numel() < cap:
-                d["buffers"][slot] = torch.empty(cap, dtype=torch.uint8, device=t.device)
-            size = d["sizes"][slot:slot + 1]
-            surfel_png.encode_png(t, out=d["buffers"][slot], size=size)
-            d["host_size"][slot:slot + 1].copy_(size, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-        return event
+        if self._device is None:
+            self._device = _f.EncodedStream(t.device, self.ring)
+        elif self._device.device != t.device:
+            raise ValueError("FrameWriter(png='device'): frames of one writer must live on one device (%s, then %s)" % (self._device.device, t.device))
+        return self._device.encode(slot, surfel_png.capacity(*t.shape), lambda out, size: surfel_png.encode_png(t, out=out, size=size))
 
     def _write_device(self, slot, path, event):
         try:
-            d = self._device
-            event.synchronize()
-            n = int(d["host_size"][slot])
-            host = self._buffer(slot, n, True)
-            with torch.cuda.device(d["device"]), torch.cuda.stream(d["stream"]):
-                host.copy_(d["buffers"][slot][:n], non_blocking=True)
-                done = torch.cuda.Event()
-                done.record()
-            done.synchronize()
-            self._store(path, memoryview(host.numpy()))
+            self._store(path, self._device.fetch(slot, event))
         except BaseException as e:
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            self._ring.park(e)
         finally:
-            self._release(slot)
+            self._ring.release(slot)
 
     def _store(self, path, data):
         with open(path, "wb") as f:
@@ -367,11 +325,9 @@ class FrameWriter:
             with open(path, "wb") as f:
                 img.save(f, kind)
         except BaseException as e:
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            self._ring.park(e)
         finally:
-            self._release(slot)
+            self._ring.release(slot)
 
     def _drain(self):
         pool, self._pool = self._pool, None
@@ -383,9 +339,7 @@ class FrameWriter:
 
     def close(self):
         self._drain()
-        if self._error is not None:
-            e, self._error = self._error, None
-            raise e
+        self._ring.reraise()
 
 
 def _folders(out_dir, names):

@@ -25,8 +25,7 @@ def scratch_bytes(H, W, C):
 
 
 def _frame(img):
-    if not torch.is_tensor(img) or not img.is_cuda:
-        raise RuntimeError("surfel_png: tensors must live on a HIP device (got %s)" % (img.device if torch.is_tensor(img) else type(img).__name__))
+    img = _n.device_tensor("surfel_png", img)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] not in (1, 3):
         raise ValueError("surfel_png: a uint8 [H, W, 1 or 3] frame expected, got %s %s" % (img.dtype, tuple(img.shape)))
     return img.detach().contiguous()
@@ -59,14 +58,11 @@ def encode_png(img, out=None, scratch=None, size=None):
     t = _frame(img)
     H, W, Cn = (int(v) for v in t.shape)
     cap, nscratch = capacity(H, W, Cn), scratch_bytes(H, W, Cn)
-    if out is None:
-        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < cap:
-        raise ValueError("encode_png: out must be a contiguous uint8 tensor of at least %d elements" % cap)
+    out = _n.uint8_buffer("encode_png", out, cap, t.device, at_least=True)
     if scratch is None:
         scratch = _cached_scratch(t.device, (H, W, Cn), nscratch)
-    elif scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous() or scratch.numel() < nscratch:
-        raise ValueError("encode_png: scratch must be a contiguous uint8 tensor of at least %d elements" % nscratch)
+    else:
+        _n.uint8_buffer("encode_png", scratch, nscratch, t.device, "scratch", at_least=True)
     if size is None:
         size = torch.empty(1, dtype=torch.int64, device=t.device)
     _n.call(t.device, "surfel_png_encode", H, W, Cn, t, out, out.numel(), size, scratch, scratch.numel())
@@ -76,4 +72,4 @@ def encode_png(img, out=None, scratch=None, size=None):
 def png_bytes(img):
     """The PNG file of a device frame as bytes: encode_png, then wait and copy exactly that many bytes."""
     buf, size = encode_png(img)
-    return buf[:int(size.item())].cpu().numpy().tobytes()
+    return _n.file_bytes(buf, size)

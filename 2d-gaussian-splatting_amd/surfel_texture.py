@@ -286,10 +286,7 @@ def resolve(mesh, lay, acc, blend="average", background=(0.0, 0.0, 0.0), out=Non
     """(atlas uint8 [Ha, Wa, 3], stats int64 [2] = owned and seen texels), on the device (TEXTURE.md §Resolve)"""
     verts, tris = _mesh(mesh)
     acc = _check_acc(acc, lay)
-    if out is None:
-        out = torch.empty((lay.height, lay.width, 3), dtype=torch.uint8, device=verts.device)
-    elif _dev(out, "out").dtype != torch.uint8 or out.numel() != lay.height * lay.width * 3 or not out.is_contiguous():
-        raise ValueError("surfel_texture: out must be a contiguous uint8 tensor of %d elements" % (lay.height * lay.width * 3))
+    out = _n.uint8_buffer("surfel_texture", out if out is None else _dev(out, "out"), lay.height * lay.width * 3, verts.device)
     stats = torch.empty(2, dtype=torch.int64, device=verts.device)
     bg = [float(x) for x in background]
     cols = shown_colors("surfel_texture", mesh, verts.shape[0])
@@ -331,10 +328,7 @@ def shade(tmesh, key, w2c, sample_intrinsics, H, W, ssaa=1, background=(1.0, 1.0
     if w.shape[0] != key.shape[0]:
         raise ValueError("surfel_texture: %d cameras for %d key images" % (w.shape[0], key.shape[0]))
     n = key.shape[0]
-    if out is None:
-        out = torch.empty((n, int(H), int(W), 3), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.numel() != n * int(H) * int(W) * 3 or not out.is_contiguous():
-        raise ValueError("surfel_texture: out must be a contiguous uint8 tensor of %d elements" % (n * int(H) * int(W) * 3))
+    out = _n.uint8_buffer("surfel_texture", out, n * int(H) * int(W) * 3, dev)
     bg = [float(x) for x in background]
     _n.call(dev, "surfel_texture_shade", verts.shape[0], tris.shape[0], verts, tris, uv.contiguous(), atlas.contiguous(), atlas.shape[1], atlas.shape[0], n,
             w, k, k.shape[0], int(H), int(W), s, key, bg[0], bg[1], bg[2], out)

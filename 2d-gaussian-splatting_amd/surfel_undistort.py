@@ -103,9 +103,7 @@ def undistort(src, q, pinhole, size):
     sees it; size = (W2, H2).  Pixels that look outside the source are 0 in every channel."""
     if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() != 3:
         raise ValueError("expected a uint8 [H, W, C] tensor")
-    if src.device.type != "cuda":
-        raise RuntimeError("libsurfel_hip: tensors must live on a HIP device (got %s)" % src.device)
-    src = src.contiguous()
+    src = _n.device_tensor("libsurfel_hip", src).contiguous()
     H, W, Cn = (int(v) for v in src.shape)
     W2, H2 = int(size[0]), int(size[1])
     qa = (C.c_double * 12)(*[float(v) for v in np.asarray(q, np.float64).reshape(12)])

@@ -8,13 +8,14 @@ frame — travel to the host, where VideoWriter appends them as the chunks of a 
 import queue
 import struct
 import threading
-import time
 
 import torch
 
+import surfel_frames as _f
 import surfel_native as _n
 
 _n.load()
+
 
 def capacity(H, W):
     """surfel_jpeg_capacity: an upper bound of the file size of an H x W frame at any quality"""
@@ -27,8 +28,7 @@ def scratch_bytes(H, W):
 
 
 def _frame(img):
-    if not torch.is_tensor(img) or not img.is_cuda:
-        raise RuntimeError("surfel_video: tensors must live on a HIP device (got %s)" % (img.device if torch.is_tensor(img) else type(img).__name__))
+    img = _n.device_tensor("surfel_video", img)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
         raise ValueError("surfel_video: a uint8 [H, W, 3] frame expected, got %s %s" % (img.dtype, tuple(img.shape)))
     return img.detach().contiguous()
@@ -42,10 +42,7 @@ def encode_jpeg(img, quality=95, out=None, size=None):
     t = _frame(img)
     H, W = int(t.shape[0]), int(t.shape[1])
     cap, nscratch = capacity(H, W), scratch_bytes(H, W)
-    if out is None:
-        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < cap:
-        raise ValueError("encode_jpeg: out must be a contiguous uint8 tensor of at least %d elements" % cap)
+    out = _n.uint8_buffer("encode_jpeg", out, cap, t.device, at_least=True)
     if size is None:
         size = torch.empty(1, dtype=torch.int64, device=t.device)
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=t.device)
@@ -56,7 +53,7 @@ def encode_jpeg(img, quality=95, out=None, size=None):
 def jpeg_bytes(img, quality=95):
     """The JFIF file of a device frame as bytes: encode_jpeg, then wait and copy exactly that many bytes."""
     buf, size = encode_jpeg(img, quality)
-    return buf[:int(size.item())].cpu().numpy().tobytes()
+    return _n.file_bytes(buf, size)
 
 
 # ------------------------------------------------------------------------------------------------ Motion-JPEG AVI
@@ -82,20 +79,18 @@ class VideoWriter:
         self.path = path
         self.frames = 0                         # chunks in the file
         self.submitted = 0
-        self.wait_s = 0.0                       # time add_frame() spent waiting for a free buffer
         self._largest = 0
         self._file = open(path, "wb")
         self._file.write(self._headers(0, 0, 0))
         self._pos = _MOVI_FOURCC + 4
         self._index = []                        # (offset relative to the 'movi' fourcc, size)
-        self._error = None
-        self._slots = None                      # device side, made by the first add_frame
-        self._free = threading.Semaphore(self.ring)
-        self._idle = list(range(self.ring))
-        self._lock = threading.Lock()
+        self._device = None                     # the device side (surfel_frames.EncodedStream), made by the first add_frame
+        self._ring = _f.SlotRing(self.ring)
         self._queue = queue.Queue()
         self._thread = threading.Thread(target=self._run, name="video-writer", daemon=True)
         self._thread.start()
+
+    wait_s = property(lambda self: self._ring.wait_s, doc="time add_frame() spent waiting for a free buffer")
 
     def __enter__(self):
         return self
@@ -137,18 +132,6 @@ class VideoWriter:
         self.frames = len(self._index)
 
     # ---- the thread
-    def _fetch(self, slot, event):
-        """the finished file of a ring slot as a memoryview of pinned memory (thread side)"""
-        s = self._slots
-        event.synchronize()
-        n = int(s["host_size"][slot])
-        if s["pinned"] is None or s["pinned"].numel() < n:
-            s["pinned"] = torch.empty(max(n, 2 * (0 if s["pinned"] is None else s["pinned"].numel())), dtype=torch.uint8, pin_memory=True)
-        with torch.cuda.device(s["device"]), torch.cuda.stream(s["stream"]):
-            s["pinned"][:n].copy_(s["buffers"][slot][:n], non_blocking=True)
-            s["stream"].synchronize()
-        return memoryview(s["pinned"].numpy())[:n]
-
     def _run(self):
         while True:
             item = self._queue.get()
@@ -156,51 +139,29 @@ class VideoWriter:
                 return
             kind, payload, event = item
             try:
-                if self._error is None:
-                    self._append(payload if kind == "bytes" else self._fetch(payload, event))
+                if self._ring.error is None:
+                    self._append(payload if kind == "bytes" else self._device.fetch(payload, event))
             except BaseException as e:
-                if self._error is None:
-                    self._error = e
+                self._ring.park(e)
             finally:
                 if kind == "slot":
-                    with self._lock:
-                        self._idle.append(payload)
-                    self._free.release()
+                    self._ring.release(payload)
 
     # ---- the caller's side
-    def _device_side(self, device):
-        cap = capacity(self.H, self.W)
-        with torch.cuda.device(device):
-            self._slots = dict(device=device, stream=torch.cuda.Stream(device=device), pinned=None,
-                               buffers=[torch.empty(cap, dtype=torch.uint8, device=device) for _ in range(self.ring)],
-                               sizes=torch.zeros(self.ring, dtype=torch.int64, device=device),
-                               host_size=torch.zeros(self.ring, dtype=torch.int64).pin_memory())
-
     def add_frame(self, img):
         t = _frame(img)
         if tuple(t.shape) != (self.H, self.W, 3):
             raise ValueError("VideoWriter.add_frame: a [%d, %d, 3] frame expected, got %s" % (self.H, self.W, tuple(t.shape)))
         if self._thread is None:
             raise RuntimeError("VideoWriter.add_frame after close()")
-        if self._slots is None:
-            self._device_side(t.device)
-        t0 = time.perf_counter()
-        self._free.acquire()
-        self.wait_s += time.perf_counter() - t0
-        with self._lock:
-            slot = self._idle.pop()
-        s = self._slots
+        if self._device is None:
+            self._capacity = capacity(self.H, self.W)
+            self._device = _f.EncodedStream(t.device, self.ring)
+        slot = self._ring.acquire()
         try:
-            with torch.cuda.device(t.device):
-                size = s["sizes"][slot:slot + 1]
-                encode_jpeg(t, self.quality, out=s["buffers"][slot], size=size)
-                s["host_size"][slot:slot + 1].copy_(size, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record()
+            event = self._device.encode(slot, self._capacity, lambda out, size: encode_jpeg(t, self.quality, out=out, size=size))
         except BaseException:
-            with self._lock:
-                self._idle.append(slot)
-            self._free.release()
+            self._ring.release(slot)
             raise
         self.submitted += 1
         self._queue.put(("slot", slot, event))
@@ -228,10 +189,8 @@ class VideoWriter:
             f.write(self._headers(len(self._index), self._pos - _MOVI_FOURCC, total - 8))
         finally:
             f.close()
-            self._slots = None
+            self._device = None
 
     def close(self):
         self._finish()
-        if self._error is not None:
-            e, self._error = self._error, None
-            raise e
+        self._ring.reraise()

@@ -17,6 +17,7 @@ import time
 
 import torch
 
+import surfel_frames as _f
 import surfel_native as _n
 import surfel_path as _sp
 
@@ -75,10 +76,7 @@ def net_image(render_pkg, mode, out=None):
     planes = 3 if name in ("Edge", "Curvature") else 1
     if src.numel() != planes * H * W:
         raise ValueError("net_image: %s needs %d plane(s), got %s" % (name, planes, tuple(src.shape)))
-    if out is None:
-        out = torch.empty((H, W, 3), dtype=torch.uint8, device=src.device)
-    elif out.dtype != torch.uint8 or out.numel() != H * W * 3 or not out.is_contiguous():
-        raise ValueError("net_image: out must be a contiguous uint8 tensor of %d elements" % (H * W * 3))
+    out = _n.uint8_buffer("net_image", out, H * W * 3, src.device)
     nbytes = scratch_bytes(H, W)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
     if planes == 1:
@@ -180,7 +178,6 @@ class Viewer:
         self.conn = None
         self.frames = 0
         self._pinned = None
-        self._event = None
 
     @classmethod
     def attached(cls, sock, timeout=DEFAULT_TIMEOUT, device="cuda", items=RENDER_ITEMS, mesh=None, texture=None):
@@ -220,17 +217,8 @@ class Viewer:
 
     def _to_host(self, image):
         """The bytes of a device image in the pinned buffer: a non-blocking copy and a wait for the event behind it."""
-        n = image.numel()
-        if self._pinned is None or self._pinned.numel() < n:
-            self._pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-        host = self._pinned[:n]
-        with torch.cuda.device(image.device):
-            host.copy_(image.reshape(-1), non_blocking=True)
-            if self._event is None:
-                self._event = torch.cuda.Event()
-            self._event.record()
-        self._event.synchronize()
-        return memoryview(host.numpy())
+        self._pinned, view = _f.to_pinned(image.reshape(-1), self._pinned)
+        return view
 
     def _mesh_mode(self, render_mode):
         """the surfel_meshview mode of a menu entry that shows the mesh (an index into this viewer's items, or a name); None for the others"""

@@ -1,7 +1,9 @@
 """The mesh tools' refusal of anything but a device tensor, word for word: every module's first-checking entry is given a CPU tensor and a
 numpy array and must raise RuntimeError with the text below — the strings the modules carried before the check moved into
-surfel_native.device_tensor, written out here and not derived from it.  No device is needed: the check comes before any device call."""
+surfel_native.device_tensor, written out here and not derived from it.  No device is needed: the check comes before any device call.
+The frame modules (PNG, video, path frames) follow: the same check without an argument's name."""
 import importlib
+import os
 
 import numpy as np
 import pytest
@@ -57,4 +59,33 @@ def test_module_refuses_host_arrays(name, entry, cpu_text, numpy_text):
     for x, text in ((torch.zeros((4, 3)), cpu_text), (np.zeros((4, 3), np.float32), numpy_text)):
         with pytest.raises(RuntimeError) as e:
             entry(P, x)
+        assert type(e.value) is RuntimeError and str(e.value) == text
+
+
+def _add_frame(P, x, tmp_path):
+    with P.VideoWriter(os.path.join(tmp_path, "refused.avi"), 4, 3) as vw:
+        vw.add_frame(x)
+
+
+# the frame modules: the entry as f(module, x, tmp_path), and the module name the message starts with
+FRAME_CASES = [
+    ("surfel_png", "encode_png", lambda P, x, tmp: P.encode_png(x)),
+    ("surfel_png", "png_bytes", lambda P, x, tmp: P.png_bytes(x)),
+    ("surfel_video", "encode_jpeg", lambda P, x, tmp: P.encode_jpeg(x)),
+    ("surfel_video", "VideoWriter.add_frame", _add_frame),
+    ("surfel_path", "quantize_u8", lambda P, x, tmp: P.quantize_u8(x)),
+    ("surfel_path", "colorize_depth", lambda P, x, tmp: P.colorize_depth(x, 0.0, 1.0)),
+    ("surfel_path", "order_stats", lambda P, x, tmp: P.order_stats(x, [0])),
+]
+FRAME_TEXTS = {"surfel_png": ("surfel_png: tensors must live on a HIP device (got cpu)", "surfel_png: tensors must live on a HIP device (got ndarray)"),
+               "surfel_video": ("surfel_video: tensors must live on a HIP device (got cpu)", "surfel_video: tensors must live on a HIP device (got ndarray)"),
+               "surfel_path": ("surfel_path: tensors must live on a HIP device (got cpu)", "surfel_path: tensors must live on a HIP device (got ndarray)")}
+
+
+@pytest.mark.parametrize("name,entry", [(c[0], c[2]) for c in FRAME_CASES], ids=[c[1] for c in FRAME_CASES])
+def test_frame_entry_refuses_host_arrays(name, entry, tmp_path):
+    P = importlib.import_module(name)
+    for x, text in zip((torch.zeros((4, 3, 3), dtype=torch.uint8), np.zeros((4, 3, 3), np.uint8)), FRAME_TEXTS[name]):
+        with pytest.raises(RuntimeError) as e:
+            entry(P, x, str(tmp_path))
         assert type(e.value) is RuntimeError and str(e.value) == text
