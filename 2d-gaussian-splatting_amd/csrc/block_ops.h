@@ -18,8 +18,8 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_reduce(v,
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return max(a, b); }); }
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return min(a, b); }); }
 
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {      // inclusive scan over the 64 lanes of a wave
-    const int lane = threadIdx.x & 63;
+// inclusive scan over the 64 lanes of a wave (lane: threadIdx.x & 63, for callers that hold it already)
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane) {
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t o = __shfl_up(v, off, 64);
@@ -27,6 +27,7 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {      // inclusiv
     }
     return v;
 }
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) { return wave_incl_sum(v, threadIdx.x & 63); }
 
 // exclusive scan of v over the workgroup; total = the sum
 template <int NT>

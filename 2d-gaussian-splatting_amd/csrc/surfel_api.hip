@@ -117,6 +117,10 @@ struct BinState {    // per-instance state ("binningBuffer"); point_list is alwa
         if (total) *total = c.size();
         return b;
     }
+    // value buffers (a, b) of the tile sort of n instances, assigned so that its ping-pong ends in point_list: emission writes a
+    std::pair<uint32_t*, uint32_t*> sort_vals(size_t n, int end_bit) const {
+        return radix_sort_result_buffer(n, 0, end_bit) == 1 ? std::make_pair(vals_alt, point_list) : std::make_pair(point_list, vals_alt);
+    }
 };
 
 struct ImgState {    // per-pixel / per-tile state ("imgBuffer")
@@ -333,9 +337,7 @@ int alloc_bin(size_t n, size_t sort_bytes, bool stream, surfel_alloc_fn binning_
 int bin_capacity(const PreprocessArgs& pa, int end_bit, int64_t cap, int64_t maxR, const GeomState& geom, const BinState& bin,
                  const ImgState& img, uint32_t* hR, hipEvent_t evR, StageTimer& tm, hipStream_t s) {
     uint32_t* n_dev = img.total + 2 * R_SLOTS;      // written by bin_emit_kernel
-    const bool odd = radix_sort_result_buffer((size_t)cap, 0, end_bit) == 1;
-    uint32_t* va = odd ? bin.vals_alt : bin.point_list;
-    uint32_t* vb = odd ? bin.point_list : bin.vals_alt;
+    const auto [va, vb] = bin.sort_vals((size_t)cap, end_bit);
     tm.begin();
     launch_bin_emit(pa.P, geom.tiles_touched, geom.rects, geom.offsets, geom.rec, bin.keys_a, va, pa.gx, (size_t)cap, bin.sort_temp, end_bit,
                     n_dev, hR + kPinnedTotal, s);
@@ -378,11 +380,8 @@ int64_t bin_exact(const PreprocessArgs& pa, int end_bit, int per_tile, int64_t R
     }
     if (int e = alloc_bin((size_t)R, radix_sort_scratch_bytes((size_t)R), stream, binning_alloc, binning_user, bin)) return e;
     if (R == 0) return 0;
-    // (3) stable sort on the tile-id bits only: depth order inside every tile is preserved.  The value buffers
-    // are assigned so that the ping-pong ends in bin->point_list.
-    const bool odd = radix_sort_result_buffer((size_t)R, 0, end_bit) == 1;      // result lands in the b buffers
-    uint32_t* va = odd ? bin->vals_alt : bin->point_list;
-    uint32_t* vb = odd ? bin->point_list : bin->vals_alt;
+    // (3) stable sort on the tile-id bits only: depth order inside every tile is preserved
+    const auto [va, vb] = bin->sort_vals((size_t)R, end_bit);
     tm.begin();
     launch_emit_instances(pa.P, geom.rec, geom.rects, order, pa.pack_tiles ? ((1u << PACK_ID_BITS) - 1u) : 0xffffffffu, geom.offsets, bin->keys_a, va, pa.gx,
                           reinterpret_cast<uint32_t*>(bin->sort_temp), (uint32_t)radix_sort_head_words((size_t)R), s);

@@ -1,57 +1,75 @@
-// surfel_sort.hip — stable LSD radix sort of (u32 key, u32 value) pairs for gfx950: ONE launch per 8-bit pass.
+// surfel_sort.hip — stable LSD radix sort of (u32 key, u32 value) pairs for gfx950, 8 bits per pass, and what the binning builds on it:
+// the emission scan (scan_gather_kernel), the per-tile depth sort (tile_depth_sort_kernel) and the capacity path's bin_emit_kernel.
 //
-// Why not rocPRIM here: the two sorts on the hot path are small and oddly shaped — P surfels by 32 depth bits and R
-// instances by the 12-17 tile-id bits — and at BASELINE configs[1] (300 k surfels / 0.6 M instances) every extra
-// launch costs more than the bytes it moves.  Structure ("onesweep"):
-//   os_hist   : digit histograms of ALL passes in one sweep over the keys (the multiset of digits of a pass does not
-//               depend on the order earlier passes leave behind); also clears the look-back state.  Callers that
-//               produce the keys themselves can fill the histogram on the fly and skip this launch.
-//   os_pass   : one launch per pass.  A 1024-thread workgroup takes the next 4096-item tile (ticket order = input order), ranks
-//               its items with wave64 match-by-ballot (no atomics, order-preserving => stable), publishes its digit
-//               counts, and obtains the counts of all earlier tiles by decoupled look-back over their published
-//               (aggregate | inclusive-prefix) words — one 32-bit word per (tile, digit) carrying flag and value, stored
-//               and loaded at agent scope, so there is no separate payload to order.  Predecessor tiles hold smaller
-//               tickets, i.e. they are already running, so the spin always terminates.
-// The tile's items pass through LDS in tile-local sorted order and leave as same-digit runs written by consecutive lanes.
-// Traffic per pass: 16 B/item + 1 KB of status per tile.
-// The look-back form is used while the whole grid is (nearly) resident (n <= RS_ONESWEEP_MAX): there a pass costs
-// 16 us instead of 30 us for three launches.  Beyond that every tile is resident and publishing at once, a tile's look-back reads
-// O(tiles) words per digit and the chain throttles the scatter (measured at 2.2 M and 10 M items, both rounds 2 and 6), so
-// large inputs take three launches per pass:
-//   rs_hist_fat (digit counts per tile) -> rs_scan (one workgroup per digit over the tiles) -> the same tile body (os_pass_fat<false>).
-// [r6] Until round 6 the large path scattered from registers (2048-item tiles, a digit's 8 items per tile stored by whichever lanes
-// ranked them: 64 lines per store instruction, 1.2 TB/s per pass) and lost to rocPRIM on tile-id sorts; through LDS it reaches
-// 2.0 TB/s per pass at 8 M items (profiles/r06_sort_ab.jsonl: C4 depth sort + scan 196 -> 157 us, tile sort 169 (rocPRIM) -> 130 us).
+// Why not rocPRIM everywhere: the sorts on the hot path are small and oddly shaped — P surfels by 32 depth bits and R instances by the
+// 12-17 tile-id bits — and at BASELINE configs[1] (300 k surfels / 0.6 M instances) every extra launch costs more than the bytes it moves.
+//
+// One tile body serves every pass (os_pass_fat_kernel): a 1024-thread workgroup takes a tile of 1024 x 4 = 4096 items, ranks them with
+// the wave64 match-by-ballot (wave_digit_rank: no atomics, order-preserving => stable), passes them through LDS in tile-local sorted order
+// and stores them as same-digit runs written by consecutive lanes (a digit's run in a tile is 16 items = 64 B on average).  What differs
+// with the input size is where a tile learns the counts of the tiles in front of it:
+//   n <= 2^20 (RS_LOOKBACK_MAX), "look-back": ONE launch per pass.
+//     os_hist_kernel : digit histograms of ALL passes in one sweep over the keys (the multiset of digits of a pass does not depend on the
+//                      order earlier passes leave behind); also clears the look-back state.  Callers that produce the keys themselves
+//                      fill the histogram on the fly and skip this launch (bin_emit_kernel).
+//     os_pass_fat_kernel<true> : tiles are taken by ticket (ticket order = input order); a tile publishes its digit counts and obtains
+//                      those of all earlier tiles by decoupled look-back over their published (aggregate | inclusive-prefix) words — one
+//                      32-bit word per (tile, digit) carrying flag and value, stored and loaded at agent scope, so there is no separate
+//                      payload to order.  Predecessor tiles hold smaller tickets, i.e. they are already running: the spin terminates.
+//     Traffic per pass: 16 B/item + 1 KB of status per tile; a pass costs 16 us where three launches cost 30 us.
+//   n > 2^20: all tiles would be resident and publishing at once, a tile's look-back reads O(tiles) words per digit and the chain throttles
+//     the scatter (measured at 2.2 M and 10 M items, rounds 2 and 6), so a pass is three launches:
+//     rs_hist_fat_kernel (digit counts per tile) -> rs_scan_kernel (one workgroup per digit over the tiles) -> os_pass_fat_kernel<false>.
+//     Through LDS the scatter reaches 2.0 TB/s per pass at 8 M items, against 1.2 TB/s for stores from the lanes that ranked the items
+//     (profiles/r06_sort_ab.jsonl: C4 depth sort + scan 196 -> 157 us, tile sort 169 (rocPRIM) -> 130 us).
+//   n > 2^20 may also go to rocprim::radix_sort_pairs: the large_sort rule below (use_rocprim).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "block_ops.h"
 #include "surfel_common.h"
 #include "surfel_kernels.h"
 
 namespace surfel {
 
-constexpr size_t RS_ONESWEEP_MAX_ITEMS = (size_t)1 << 20;
-// largest input the one-launch-per-pass look-back passes take (above: histogram + scan + scatter per pass, or rocPRIM: use_rocprim).
-// [r6] raised to 2^22 for the 2.2 M-key depth sort of the garden state it LOST: 0.220 -> 0.248 ms (profiles/r06_ab_preprocess_dma.jsonl)
-constexpr size_t g_onesweep_max = RS_ONESWEEP_MAX_ITEMS;
-// Large inputs (n > RS_ONESWEEP_MAX: the P-sized depth sort at C4 / C5 and the R-sized tile sort of 1e7 - 1e8 instances) can be
-// handed to rocprim::radix_sort_pairs (the north star names rocPRIM for the global key sort) instead of the three-launch path
-// below: surfel_set_option("large_sort", 1).  Both are stable LSD sorts on [begin_bit, end_bit): results are identical.
+// ---- geometry ------------------------------------------------------------------------------------------------------------------
+constexpr int RS_BITS = 8;
+constexpr int RS_RADIX = 1 << RS_BITS;
+constexpr int RS_MAX_PASSES = 4;
+constexpr int RS_THREADS = 256;      // workgroup of os_hist_kernel, rs_scan_kernel, scan_gather_kernel and tile_depth_sort_kernel
+// The pass tile: 1024 x 4 = 4096 items — 128 workgroups for an 800x800 frame's 0.5 M pairs.  Round 5 measured it against 1024 x 8,
+// 1024 x 3, 1024 x 2, 768 x 4, 512 x 16, 512 x 8, 512 x 4: 36.4 us for the two passes against 39.0 / 38.2 / 42.7 / 38.3 / 41.0 / 37.5 / 45.1.
+constexpr int FT_THREADS = 1024, FT_IPT = 4, FT_TILE = FT_THREADS * FT_IPT, FT_WAVES = FT_THREADS / 64;
+constexpr int FT_LB = 32;      // look-back window: at most 256 tiles exist, all resident and publishing at about the same moment
+static inline uint32_t ft_nblocks(size_t n) { return (uint32_t)((n + FT_TILE - 1) / FT_TILE); }
+// 256 x 8 = 2048 items: the tile of os_hist_kernel's launch, and the unit the look-back status is SIZED in — 256 words per pass and 2048
+// items.  The passes index it by their 4096-item tiles and so use the first half of every pass's slice; the sizes stay as they are
+// (callers carve their scratch by them), shrinking them is a change of its own.
+constexpr int HIST_IPT = 8, HIST_TILE = RS_THREADS * HIST_IPT;
+static inline uint32_t hist_nblocks(size_t n) { return (uint32_t)((n + HIST_TILE - 1) / HIST_TILE); }
+// largest input of the look-back passes.  (Round 6 raised it to 2^22 for the 2.2 M-key depth sort of the garden state and LOST:
+// 0.220 -> 0.248 ms, profiles/r06_ab_preprocess_dma.jsonl.)
+constexpr size_t RS_LOOKBACK_MAX = (size_t)1 << 20;
+static inline bool rs_lookback(size_t n) { return n <= RS_LOOKBACK_MAX; }
+constexpr uint32_t ST_AGG = 1u << 30, ST_PREFIX = 2u << 30, ST_VALUE = (1u << 30) - 1u;      // status word = flag | 30-bit value
+
+// ---- large_sort: who sorts n > 2^20 items ----------------------------------------------------------------------------------------
+// Large inputs (the P-sized depth sort at C4 / C5 and the R-sized tile sort of 1e7 - 1e8 instances) can be handed to
+// rocprim::radix_sort_pairs (the north star names rocPRIM for the global key sort) instead of the three launches per pass:
+// surfel_set_option("large_sort", 1).  Both are stable LSD sorts on [begin_bit, end_bit): results are identical.
 int g_large_sort_impl = 2;      // 0 own, 1 rocPRIM, 2 auto
 void set_large_sort_impl(int v) { g_large_sort_impl = v < 0 ? 0 : (v > 3 ? 2 : v); }      // 3: rocPRIM for every size (measurement only)
 // auto (measured on MI355X, profiles/r06_sort_ab.jsonl): the library's own passes up to 2^25 items (8.1 M tile-id pairs: 130 vs
-// 168 us; 2 M / 10 M depth keys: 0.157 vs 0.216 / 0.584 vs 0.651 ms incl. the scan), rocPRIM above (1.3e8 tile-id pairs: 2.04 vs
-// 2.44 ms — at that size 8192-item tiles draw level, 2.02, but lose below).
-static inline bool use_rocprim(size_t n, int begin_bit, int end_bit) {
+// 168 us; 2 M / 10 M depth keys: 0.157 vs 0.216 / 0.584 vs 0.651 ms incl. the scan), rocPRIM above (1.3e8 tile-id pairs: 2.04 vs 2.44 ms).
+static inline bool use_rocprim(size_t n, int begin_bit) {
     // key fields that do not start at bit 0 always take the library's own passes: rocprim::radix_sort_pairs of this ROCm returned
     // wrongly ordered values for [24, 32), [30, 32) and [31, 32) at >= 4096 items (scripts/dbg/rocprim_small.py; fields starting at
     // bit 0 — all the hot path sorts on — are exact at every size tested)
     if (begin_bit != 0) return false;
     if (g_large_sort_impl == 3) return true;
-    if (n <= g_onesweep_max) return false;
+    if (rs_lookback(n)) return false;
     if (g_large_sort_impl != 2) return g_large_sort_impl == 1;
     return n > ((size_t)1 << 25);
 }
@@ -67,43 +85,46 @@ static size_t rocprim_sort_temp_bytes(size_t n) {
     return bytes;
 }
 
-constexpr int RS_THREADS = 256;
-// items per thread: 8 (2048-item tiles) for large inputs — long same-digit store runs, 1 KB of status per 16 KB of
-// pairs; 2 (512-item tiles) for small ones, where the whole grid is resident and the critical path of one tile
-// (sweeps x ballot ranking at one wave per SIMD) is what a pass costs.
-// (512-item tiles were measured 2x SLOWER at 0.3-0.6 M items: 4x the tickets, status words and look-back depth.)
-constexpr int RS_IPT = 8;
-constexpr int RS_TILE = RS_THREADS * RS_IPT;
-static inline bool rs_onesweep(size_t n) { return n <= g_onesweep_max; }
-constexpr int RS_BITS = 8;
-constexpr int RS_RADIX = 1 << RS_BITS;
-constexpr int RS_MAX_PASSES = 4;
-constexpr uint32_t ST_AGG = 1u << 30, ST_PREFIX = 2u << 30, ST_VALUE = (1u << 30) - 1u;
-
-// scratch layout (u32 words): ghist[RS_MAX_PASSES][256] | ticket[RS_MAX_PASSES] (+pad to 64) | status[passes][nblocks][256]
-constexpr size_t RS_HEAD_WORDS = RS_MAX_PASSES * RS_RADIX + 64;
-
-static inline uint32_t rs_nblocks(size_t n) { return (uint32_t)((n + RS_TILE - 1) / RS_TILE); }
-
-size_t radix_sort_scratch_bytes(size_t n) {
-    if (!rs_onesweep(n)) {
-        const size_t own = ((size_t)RS_RADIX * rs_nblocks(n) + RS_RADIX) * sizeof(uint32_t) + 256;   // hist[digit][tile] | total[digit]
-        const size_t rp = rocprim_sort_temp_bytes(n) + 256;
-        return own > rp ? own : rp;
+// ---- the pass plan -----------------------------------------------------------------------------------------------------------------
+// The library's own passes over key bits [begin_bit, end_bit): pass p takes the digit of up to 8 bits at begin_bit + 8 p, reads buffer
+// pair p & 1 (0: a, 1: b) and writes the other.  This is the one place that states the parity: the result is in pair count() & 1.
+static inline int sort_passes(int begin_bit, int end_bit) { return (end_bit - begin_bit + RS_BITS - 1) / RS_BITS; }
+struct SortPass { int bit; uint32_t mask; const uint32_t *kin, *vin; uint32_t *kout, *vout; };
+struct PassPlan {
+    uint32_t *keys[2], *vals[2];      // [0]: a, [1]: b
+    int begin_bit, end_bit;
+    int count() const { return sort_passes(begin_bit, end_bit); }
+    int result() const { return count() & 1; }
+    SortPass pass(int p) const {
+        const int bit = begin_bit + p * RS_BITS, nb = end_bit - bit < RS_BITS ? end_bit - bit : RS_BITS, in = p & 1;
+        return {bit, (1u << nb) - 1u, keys[in], vals[in], keys[in ^ 1], vals[in ^ 1]};
     }
-    const size_t own = (RS_HEAD_WORDS + (size_t)RS_MAX_PASSES * rs_nblocks(n) * RS_RADIX) * sizeof(uint32_t) + 256;
-    const size_t rp = g_large_sort_impl == 3 ? rocprim_sort_temp_bytes(n) + 256 : 0;
-    return own > rp ? own : rp;
-}
-int radix_sort_passes(size_t, int begin_bit, int end_bit) { return (end_bit - begin_bit + RS_BITS - 1) / RS_BITS; }
+};
 // which buffer pair radix_sort_pairs_u32 will leave the result in (0: a, 1: b) — callers that need it in a particular buffer
 // assign a / b accordingly BEFORE the call
 int radix_sort_result_buffer(size_t n, int begin_bit, int end_bit) {
     if (n == 0 || end_bit <= begin_bit) return 0;
-    if (use_rocprim(n, begin_bit, end_bit)) return 1;
-    return radix_sort_passes(n, begin_bit, end_bit) & 1;
+    if (use_rocprim(n, begin_bit)) return 1;
+    return PassPlan{{}, {}, begin_bit, end_bit}.result();
 }
-size_t radix_sort_head_bytes() { return RS_HEAD_WORDS * sizeof(uint32_t); }
+
+// ---- scratch ----------------------------------------------------------------------------------------------------------------------
+// look-back (u32 words): ghist[RS_MAX_PASSES][256] | ticket[RS_MAX_PASSES] (+pad to 64) | status[RS_MAX_PASSES][hist_nblocks][256]
+// three launches       : hist[256][ft_nblocks], in the first half of 256 * hist_nblocks words | total[256]
+constexpr size_t RS_HEAD_WORDS = RS_MAX_PASSES * RS_RADIX + 64;
+size_t radix_sort_scratch_bytes(size_t n) {
+    if (!rs_lookback(n)) {
+        const size_t own = ((size_t)RS_RADIX * hist_nblocks(n) + RS_RADIX) * sizeof(uint32_t) + 256;
+        const size_t rp = rocprim_sort_temp_bytes(n) + 256;
+        return own > rp ? own : rp;
+    }
+    const size_t own = (RS_HEAD_WORDS + (size_t)RS_MAX_PASSES * hist_nblocks(n) * RS_RADIX) * sizeof(uint32_t) + 256;
+    const size_t rp = g_large_sort_impl == 3 ? rocprim_sort_temp_bytes(n) + 256 : 0;
+    return own > rp ? own : rp;
+}
+// The look-back head (ghist + tickets) has to be zero when a sort starts.  Callers whose previous kernel can clear
+// radix_sort_head_words(n) words at the start of the scratch pass head_zeroed = true and save the memset launch.
+size_t radix_sort_head_words(size_t n) { return rs_lookback(n) ? RS_HEAD_WORDS : 0; }
 
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -116,9 +137,9 @@ __global__ void __launch_bounds__(RS_THREADS) os_hist_kernel(const uint32_t* __r
     for (int p = 0; p < passes; p++) s_h[p][threadIdx.x] = 0;
     for (int p = 0; p < passes; p++) status[((size_t)p * nblocks + blockIdx.x) * RS_RADIX + threadIdx.x] = 0u;
     __syncthreads();
-    const uint32_t base = blockIdx.x * (RS_THREADS * RS_IPT);
+    const uint32_t base = blockIdx.x * HIST_TILE;
 #pragma unroll
-    for (int it = 0; it < RS_IPT; it++) {
+    for (int it = 0; it < HIST_IPT; it++) {
         const uint32_t e = base + it * RS_THREADS + threadIdx.x;
         if (e < n) {
             const uint32_t k = keys[e];
@@ -136,18 +157,16 @@ __global__ void __launch_bounds__(RS_THREADS) os_hist_kernel(const uint32_t* __r
     }
 }
 
-// ---- large-n path: digit counts per 4096-item tile -> hist[digit][tile] (rs_hist_fat_kernel), then one workgroup per digit scans its row
-constexpr int FTH_THREADS = 1024;
-template <int FTH_IPT>
-__global__ void __launch_bounds__(FTH_THREADS) rs_hist_fat_kernel(const uint32_t* __restrict__ keys, uint32_t n, int shift, uint32_t mask,
-                                                                  uint32_t* __restrict__ hist, uint32_t nblocks) {
+// ---- n > 2^20: digit counts per 4096-item tile -> hist[digit][tile] (rs_hist_fat_kernel), then one workgroup per digit scans its row
+__global__ void __launch_bounds__(FT_THREADS) rs_hist_fat_kernel(const uint32_t* __restrict__ keys, uint32_t n, int shift, uint32_t mask,
+                                                                 uint32_t* __restrict__ hist, uint32_t nblocks) {
     __shared__ uint32_t s_h[RS_RADIX];
     if (threadIdx.x < RS_RADIX) s_h[threadIdx.x] = 0;
     __syncthreads();
-    const uint32_t base = blockIdx.x * (uint32_t)(FTH_THREADS * FTH_IPT);
+    const uint32_t base = blockIdx.x * (uint32_t)FT_TILE;
 #pragma unroll
-    for (int it = 0; it < FTH_IPT; it++) {
-        const uint32_t e = base + it * FTH_THREADS + threadIdx.x;
+    for (int it = 0; it < FT_IPT; it++) {
+        const uint32_t e = base + it * FT_THREADS + threadIdx.x;
         if (e < n) atomicAdd(&s_h[(keys[e] >> shift) & mask], 1u);
     }
     __syncthreads();
@@ -163,9 +182,7 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scan_kernel(uint32_t* __restric
     for (uint32_t c0 = 0; c0 < nblocks; c0 += RS_THREADS) {
         const uint32_t i = c0 + threadIdx.x;
         const uint32_t v = i < nblocks ? row[i] : 0u;
-        uint32_t x = v;                           // inclusive wave scan
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o); if (lane >= o) x += y; }
+        const uint32_t x = wave_incl_sum(v, lane);
         if (lane == 63) s_w[wave] = x;
         __syncthreads();
         uint32_t woff = 0;
@@ -179,22 +196,33 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scan_kernel(uint32_t* __restric
     if (threadIdx.x == 0) total[blockIdx.x] = s_carry;
 }
 
-// ---- the look-back pass for <= 2^20 items, fat tiles -------------------------------------------------------------------------
-// Same algorithm as os_pass_kernel<true>, 1024-thread workgroups with 4096-item tiles (8192 until round 5), and the tile's items go through LDS in
-// tile-local sorted order before they are stored.  Measured on the thin (2048-item) pass at 0.5 M items (r03g_C2_kernel_stats):
-// 18.5 us for the 4-bit digit, 30.5 us for the 8-bit digit — the difference is the scatter: a thin tile holds 8 items per 8-bit
-// digit, stored by whichever lane ranked them (64 different lines per store instruction).  Here a digit's run in a tile is
-// 16 items = 64 B, written by consecutive lanes; and the look-back chain is half as long.
-// (Round 5: 1024 x 4 = 4096-item tiles — 128 workgroups for an 800x800 frame's 0.5 M pairs instead of 64 — measured against 1024 x 8,
-// 1024 x 3, 1024 x 2, 768 x 4, 512 x 16, 512 x 8, 512 x 4: 36.4 us for the two passes against 39.0 / 38.2 / 42.7 / 38.3 / 41.0 / 37.5 / 45.1.)
-constexpr int FT_THREADS = 1024, FT_IPT = 4, FT_TILE = FT_THREADS * FT_IPT, FT_WAVES = FT_THREADS / 64;
-constexpr int FT_LB = 32;      // look-back window: at most 256 tiles exist, all resident and publishing at about the same moment
-static inline uint32_t ft_nblocks(size_t n) { return (uint32_t)((n + FT_TILE - 1) / FT_TILE); }
+// rank of this lane's item among the items with digit d the wave has ranked so far (cnt_row: the wave's own 256 counters): the lanes
+// that hold the same digit find each other by eight ballots, the first of them adds their number to the digit's counter.
+// FULL_DIGIT: the caller masks with the constant 255 (the per-tile sorter) and d < 256 is stated: worth a v_bfe and a v_and per call
+// there, and the compiler does not carry a caller's range into this body by itself once another caller's mask is a run-time value.  The
+// pass kernels do not state it: it would make them 5 and 8 instructions shorter, which nobody has timed.
+template <bool FULL_DIGIT>
+__device__ __forceinline__ uint32_t wave_digit_rank(uint32_t d, bool valid, uint32_t* cnt_row) {
+    if (FULL_DIGIT) __builtin_assume(d < (uint32_t)RS_RADIX);
+    unsigned long long mm = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < RS_BITS; b++) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long bal = __ballot(bit);
+        mm &= bit ? bal : ~bal;
+    }
+    if (!valid) mm = 0ull;
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+    const uint32_t prev = valid ? cnt_row[d] : 0u;      // same-wave LDS ops are program-ordered
+    if (valid && below == 0) cnt_row[d] = prev + (uint32_t)__popcll(mm);
+    return prev + below;
+}
 
-// LOOKBACK = false (inputs above 2^20 items, round 6): the same tile body behind the histogram + scan launches of the large-n path
-// (ghist = total[digit] from rs_scan, status = hist[digit][tile] exclusive-scanned over the 4096-item tiles, tile = blockIdx.x) — the
-// thin pass stores a digit's 8 items per tile from whichever lanes ranked them; here they leave LDS as 64-B runs.
-template <bool LOOKBACK, int IPT>
+// ---- the tile body of every pass ---------------------------------------------------------------------------------------------------
+// LOOKBACK = true (n <= 2^20): tile = ticket, ghist = the pass's digit totals (hstride words apart), status = the pass's look-back words.
+// LOOKBACK = false (n > 2^20), behind the histogram + scan launches: tile = blockIdx.x, ghist = total[digit] from rs_scan_kernel,
+// status = hist[digit][tile], exclusive-scanned over the nblocks tiles.
+template <bool LOOKBACK>
 __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                                  uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, uint32_t n,
                                                                  int shift, uint32_t mask, const uint32_t* __restrict__ ghist,
@@ -202,8 +230,7 @@ __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t*
                                                                  const uint32_t* __restrict__ n_dev, int hstride, uint2* __restrict__ ranges,
                                                                  uint32_t nblocks) {
     __shared__ uint32_t s_cnt[FT_WAVES][RS_RADIX];      // per-wave digit counts -> then per-wave tile-local offsets
-    constexpr int TILE_ITEMS = FT_THREADS * IPT;
-    __shared__ uint2 s_item[TILE_ITEMS];                   // (key, value) in tile-local sorted order
+    __shared__ uint2 s_item[FT_TILE];                   // (key, value) in tile-local sorted order
     __shared__ uint32_t s_gbase[RS_RADIX];              // global slot of a digit's first item of this tile, minus its tile-local slot
     __shared__ uint32_t s_w[4][2];
     __shared__ uint32_t s_tile;
@@ -214,34 +241,18 @@ __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t*
     __syncthreads();
     const uint32_t tile = LOOKBACK ? s_tile : blockIdx.x;
     if (n_dev) n = min(n, *n_dev);
-    if (tile * (uint32_t)TILE_ITEMS >= n) return;
-    const uint32_t wbase = tile * (uint32_t)TILE_ITEMS + wave * (64 * IPT);
-    uint32_t k[IPT], v[IPT], rank[IPT];
+    if (tile * (uint32_t)FT_TILE >= n) return;
+    const uint32_t wbase = tile * (uint32_t)FT_TILE + wave * (64 * FT_IPT);
+    uint32_t k[FT_IPT], v[FT_IPT], rank[FT_IPT];
 #pragma unroll
-    for (int it = 0; it < IPT; it++) {
+    for (int it = 0; it < FT_IPT; it++) {
         const uint32_t e = wbase + it * 64 + lane;
         const bool valid = e < n;
         k[it] = valid ? keys[e] : 0xffffffffu;
         v[it] = valid ? vals[e] : 0u;
     }
 #pragma unroll
-    for (int it = 0; it < IPT; it++) {
-        const uint32_t e = wbase + it * 64 + lane;
-        const bool valid = e < n;
-        const uint32_t d = (k[it] >> shift) & mask;
-        unsigned long long mm = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < RS_BITS; b++) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long bal = __ballot(bit);
-            mm &= bit ? bal : ~bal;
-        }
-        if (!valid) mm = 0ull;
-        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-        const uint32_t prev = valid ? s_cnt[wave][d] : 0u;   // same-wave LDS ops are program-ordered
-        rank[it] = prev + below;
-        if (valid && below == 0) s_cnt[wave][d] = prev + (uint32_t)__popcll(mm);
-    }
+    for (int it = 0; it < FT_IPT; it++) rank[it] = wave_digit_rank<false>((k[it] >> shift) & mask, wbase + it * 64 + lane < n, s_cnt[wave]);
     __syncthreads();
     uint32_t cw[FT_WAVES], cnt = 0, excl = 0, tot = 0, x = 0, y = 0;      // (threads < 256: one digit each)
     if (threadIdx.x < RS_RADIX) {
@@ -282,7 +293,7 @@ __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t*
         }
         // exclusive scans over the digits: of the digit totals (global start of a digit) and of this tile's counts (tile-local start)
         tot = ghist[(size_t)d_t * hstride];
-        x = tot; y = cnt;
+        x = tot; y = cnt;      // (two wave_incl_sum calls cost the three-launch instance two more VGPRs: the pair stays in one loop)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const uint32_t xa = __shfl_up(x, o), ya = __shfl_up(y, o);
@@ -301,7 +312,7 @@ __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t*
     }
     __syncthreads();
 #pragma unroll
-    for (int it = 0; it < IPT; it++) {
+    for (int it = 0; it < FT_IPT; it++) {
         const uint32_t e = wbase + it * 64 + lane;
         if (e < n) {
             const uint32_t d = (k[it] >> shift) & mask;
@@ -309,9 +320,9 @@ __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t*
         }
     }
     __syncthreads();
-    const uint32_t items = min((uint32_t)TILE_ITEMS, n - tile * (uint32_t)TILE_ITEMS);
+    const uint32_t items = min((uint32_t)FT_TILE, n - tile * (uint32_t)FT_TILE);
 #pragma unroll
-    for (int it = 0; it < IPT; it++) {
+    for (int it = 0; it < FT_IPT; it++) {
         const uint32_t q = (uint32_t)it * FT_THREADS + threadIdx.x;
         if (q < items) {
             const uint2 kv = s_item[q];
@@ -332,10 +343,6 @@ __global__ void __launch_bounds__(FT_THREADS) os_pass_fat_kernel(const uint32_t*
         }
     }
 }
-
-// The look-back head (ghist + tickets) has to be zero when a sort starts.  Callers whose previous kernel can clear
-// radix_sort_head_words(n) words at the start of the scratch pass head_zeroed = true and save the memset launch.
-size_t radix_sort_head_words(size_t n) { return rs_onesweep(n) ? RS_HEAD_WORDS : 0; }
 
 // ---- inclusive scan of tiles[order[k]] (single launch, decoupled look-back; status word = flag | 30-bit value) -----------
 constexpr int SC_IPT = 8, SC_TILE = RS_THREADS * SC_IPT;
@@ -365,9 +372,7 @@ __global__ void __launch_bounds__(RS_THREADS) scan_gather_kernel(const uint32_t*
         v[i] = t;
         sum += v[i];
     }
-    uint32_t x = sum;                              // inclusive scan of the per-thread sums over the workgroup
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o); if (lane >= o) x += y; }
+    const uint32_t x = wave_incl_sum(sum, lane);   // inclusive scan of the per-thread sums over the workgroup
     if (lane == 63) s_w[wave] = x;
     __syncthreads();
     uint32_t woff = 0;
@@ -389,10 +394,7 @@ __global__ void __launch_bounds__(RS_THREADS) scan_gather_kernel(const uint32_t*
                 const int nready = ready == ~0ull ? 64 : __builtin_ctzll(~ready);       // leading run of published words
                 const int firstp = pref ? __builtin_ctzll(pref) : 64;
                 const int take = min(nready, firstp + 1);                                // up to and including the first prefix
-                uint32_t c = lane < take ? (sw & ST_VALUE) : 0u;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-                excl += c;
+                excl += wave_sum(lane < take ? (sw & ST_VALUE) : 0u);
                 if (firstp < nready) break;
                 p -= take;
                 if (take == 0) __builtin_amdgcn_s_sleep(1);
@@ -484,7 +486,7 @@ __device__ __forceinline__ void tile_sort_regs(uint32_t n, uint32_t* __restrict_
 // ---- per-tile LSD radix sort (runs longer than the network pays for) ----------------------------------------------------------
 // PRECONDITION: the run arrives in ascending surfel index (surfel-order emission, then the stable tile sort: bin_exact with per_tile,
 // bin_capacity), so a STABLE sort on the 32 depth bits alone leaves it ordered by (depth bits, surfel index) — what the network gets
-// by comparing the index explicitly.  Passes of 8 bits, ranked with the wave64 match-by-ballot of os_pass_fat_kernel; a pass whose
+// by comparing the index explicitly.  Passes of 8 bits, ranked with the wave64 match-by-ballot (wave_digit_rank); a pass whose
 // eight bits are the same in every key of the run (OR == AND) is skipped: the top byte of depths in [0.2, far) nearly always is.
 constexpr int TR_WAVES = RS_THREADS / 64;
 constexpr int TR_BITONIC_MAX = 8 * RS_THREADS;      // longest run the register network is built for
@@ -493,26 +495,10 @@ constexpr int TR_CHUNK_IPT = 8;                     // chunked form: 2048 items 
 int g_tile_radix_min = TR_RADIX_MIN;
 void set_tile_radix_min(int v) { g_tile_radix_min = v < 0 ? TR_RADIX_MIN : (v > TR_BITONIC_MAX ? TR_BITONIC_MAX : v); }
 
-// rank of this lane's item among the items with digit d the wave has ranked so far (cnt_row: the wave's own 256 counters)
-__device__ __forceinline__ uint32_t tr_rank(uint32_t d, bool valid, uint32_t* cnt_row) {
-    unsigned long long mm = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < RS_BITS; b++) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long bal = __ballot(bit);
-        mm &= bit ? bal : ~bal;
-    }
-    if (!valid) mm = 0ull;
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-    const uint32_t prev = valid ? cnt_row[d] : 0u;      // same-wave LDS ops are program-ordered
-    if (valid && below == 0) cnt_row[d] = prev + (uint32_t)__popcll(mm);
-    return prev + below;
-}
-
 // OR and AND of a value over the workgroup (s_w: 2 * TR_WAVES words; ends behind a barrier)
 __device__ __forceinline__ uint32_t tr_key_spread(uint32_t o, uint32_t a, uint32_t* s_w, int lane, int wave) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { o |= __shfl_xor(o, off); a &= __shfl_xor(a, off); }
+    o = wave_reduce(o, [](uint32_t p, uint32_t q) { return p | q; });
+    a = wave_reduce(a, [](uint32_t p, uint32_t q) { return p & q; });
     if (lane == 0) { s_w[wave] = o; s_w[TR_WAVES + wave] = a; }
     __syncthreads();
     o = 0u; a = ~0u;
@@ -523,9 +509,7 @@ __device__ __forceinline__ uint32_t tr_key_spread(uint32_t o, uint32_t a, uint32
 
 // exclusive scan of one count per thread (thread = digit) over the workgroup (s_w: TR_WAVES words; one barrier inside)
 __device__ __forceinline__ uint32_t tr_digit_scan(uint32_t cnt, uint32_t* s_w, int lane, int wave) {
-    uint32_t x = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o); if (lane >= o) x += y; }
+    const uint32_t x = wave_incl_sum(cnt, lane);
     if (lane == 63) s_w[wave] = x;
     __syncthreads();
     uint32_t excl = x - cnt;
@@ -563,7 +547,7 @@ __device__ __forceinline__ void tile_radix_lds(uint32_t n, uint32_t* __restrict_
 #pragma unroll
         for (int it = 0; it < IPT; it++) {
             uint32_t r = 0u;
-            if ((uint32_t)it < ipt) r = tr_rank((k[it] >> shift) & (RS_RADIX - 1u), true, s_cnt[wave]);
+            if ((uint32_t)it < ipt) r = wave_digit_rank<true>((k[it] >> shift) & (RS_RADIX - 1u), true, s_cnt[wave]);
             rank[it] = r;
             __builtin_amdgcn_sched_barrier(0);      // one item's ballots at a time
         }
@@ -632,7 +616,7 @@ __device__ __forceinline__ void tile_radix_chunked(uint32_t n, uint32_t* pl, con
             }
 #pragma unroll
             for (int it = 0; it < TR_CHUNK_IPT; it++) {
-                rank[it] = tr_rank((k[it] >> shift) & (RS_RADIX - 1u), wbase + (uint32_t)it * 64u + lane < n, s_cnt[wave]);
+                rank[it] = wave_digit_rank<true>((k[it] >> shift) & (RS_RADIX - 1u), wbase + (uint32_t)it * 64u + lane < n, s_cnt[wave]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             __syncthreads();
@@ -733,49 +717,37 @@ int radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, u
                          void* scratch, hipStream_t s, bool head_zeroed) {
     if (n == 0 || end_bit <= begin_bit) return 0;      // an empty key field: the input order is the sorted order
     if (n >= ST_VALUE) return -1;
-    const uint32_t nblocks = rs_nblocks(n);
-    const int passes = radix_sort_passes(n, begin_bit, end_bit);
-    if (passes > RS_MAX_PASSES) return -1;
-    int cur = 0;
-    if (use_rocprim(n, begin_bit, end_bit)) {
+    const PassPlan plan{{keys_a, keys_b}, {vals_a, vals_b}, begin_bit, end_bit};
+    if (plan.count() > RS_MAX_PASSES) return -1;
+    if (use_rocprim(n, begin_bit)) {
         size_t bytes = rocprim_sort_temp_bytes(n);
         if (rocprim::radix_sort_pairs(scratch, bytes, keys_a, keys_b, vals_a, vals_b, n, (unsigned)begin_bit, (unsigned)end_bit, s) != hipSuccess) return -1;
         return 1;
     }
-    if (!rs_onesweep(n)) {
+    const uint32_t nblocks = hist_nblocks(n), fb = ft_nblocks(n);
+    if (!rs_lookback(n)) {
         uint32_t* hist = static_cast<uint32_t*>(scratch);
         uint32_t* total = hist + (size_t)RS_RADIX * nblocks;
-        for (int p = 0; p < passes; p++) {
-            const int bit = begin_bit + p * RS_BITS;
-            const int nb = end_bit - bit < RS_BITS ? end_bit - bit : RS_BITS;
-            const uint32_t mask = (1u << nb) - 1u;
-            const uint32_t* kin = cur ? keys_b : keys_a; const uint32_t* vin = cur ? vals_b : vals_a;
-            uint32_t* kout = cur ? keys_a : keys_b; uint32_t* vout = cur ? vals_a : vals_b;
-            const uint32_t fb = ft_nblocks(n);
-            hipLaunchKernelGGL(rs_hist_fat_kernel<FT_IPT>, dim3(fb), dim3(FTH_THREADS), 0, s, kin, (uint32_t)n, bit, mask, hist, fb);
+        for (int p = 0; p < plan.count(); p++) {
+            const SortPass ps = plan.pass(p);
+            hipLaunchKernelGGL(rs_hist_fat_kernel, dim3(fb), dim3(FT_THREADS), 0, s, ps.kin, (uint32_t)n, ps.bit, ps.mask, hist, fb);
             hipLaunchKernelGGL(rs_scan_kernel, dim3(RS_RADIX), dim3(RS_THREADS), 0, s, hist, fb, total);
-            hipLaunchKernelGGL((os_pass_fat_kernel<false, FT_IPT>), dim3(fb), dim3(FT_THREADS), 0, s, kin, vin, kout, vout, (uint32_t)n, bit, mask, total, hist,
-                               (uint32_t*)nullptr, (const uint32_t*)nullptr, 1, (uint2*)nullptr, fb);
-            cur ^= 1;
+            hipLaunchKernelGGL(os_pass_fat_kernel<false>, dim3(fb), dim3(FT_THREADS), 0, s, ps.kin, ps.vin, ps.kout, ps.vout, (uint32_t)n, ps.bit, ps.mask,
+                               total, hist, (uint32_t*)nullptr, (const uint32_t*)nullptr, 1, (uint2*)nullptr, fb);
         }
-        return cur;
+        return plan.result();
     }
     uint32_t* ghist = static_cast<uint32_t*>(scratch);
     uint32_t* ticket = ghist + RS_MAX_PASSES * RS_RADIX;
     uint32_t* status = ghist + RS_HEAD_WORDS;
     if (!head_zeroed) (void)hipMemsetAsync(scratch, 0, RS_HEAD_WORDS * sizeof(uint32_t), s);
-    hipLaunchKernelGGL(os_hist_kernel, dim3(nblocks), dim3(RS_THREADS), 0, s, keys_a, (uint32_t)n, begin_bit, end_bit, passes, ghist, status, nblocks);
-    for (int p = 0; p < passes; p++) {
-        const int bit = begin_bit + p * RS_BITS;
-        const int nb = end_bit - bit < RS_BITS ? end_bit - bit : RS_BITS;
-        const uint32_t mask = (1u << nb) - 1u;
-        const uint32_t* kin = cur ? keys_b : keys_a; const uint32_t* vin = cur ? vals_b : vals_a;
-        uint32_t* kout = cur ? keys_a : keys_b; uint32_t* vout = cur ? vals_a : vals_b;
-        hipLaunchKernelGGL((os_pass_fat_kernel<true, FT_IPT>), dim3(ft_nblocks(n)), dim3(FT_THREADS), 0, s, kin, vin, kout, vout, (uint32_t)n, bit, mask,
+    hipLaunchKernelGGL(os_hist_kernel, dim3(nblocks), dim3(RS_THREADS), 0, s, keys_a, (uint32_t)n, begin_bit, end_bit, plan.count(), ghist, status, nblocks);
+    for (int p = 0; p < plan.count(); p++) {
+        const SortPass ps = plan.pass(p);
+        hipLaunchKernelGGL(os_pass_fat_kernel<true>, dim3(fb), dim3(FT_THREADS), 0, s, ps.kin, ps.vin, ps.kout, ps.vout, (uint32_t)n, ps.bit, ps.mask,
                            ghist + p * RS_RADIX, status + (size_t)p * nblocks * RS_RADIX, ticket + p, (const uint32_t*)nullptr, 1, (uint2*)nullptr, 0u);
-        cur ^= 1;
     }
-    return cur;
+    return plan.result();
 }
 
 // ---- capacity binning (small / medium frames) ------------------------------------------------------------------------------
@@ -858,27 +830,21 @@ __global__ void __launch_bounds__(BE_THREADS) bin_emit_kernel(int P, const uint3
 int radix_sort_pairs_u32_devn(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t cap, int end_bit, const uint32_t* n_dev,
                               void* scratch, uint2* ranges, hipStream_t s) {
     // scratch layout of the capacity path (u32 words): ghist[RS_MAX_PASSES][256] padded to BE_HSTRIDE | ticket (+pad to 64) | status
-    const uint32_t nblocks = rs_nblocks(cap);
-    const int passes = radix_sort_passes(cap, 0, end_bit);
+    const PassPlan plan{{keys_a, keys_b}, {vals_a, vals_b}, 0, end_bit};
+    const uint32_t nblocks = hist_nblocks(cap);
     uint32_t* ghist = static_cast<uint32_t*>(scratch);
     uint32_t* ticket = ghist + (size_t)RS_MAX_PASSES * RS_RADIX * BE_HSTRIDE;
     uint32_t* status = ghist + bin_emit_head_words();
-    int cur = 0;
-    for (int p = 0; p < passes; p++) {
-        const int bit = p * RS_BITS;
-        const int nb = end_bit - bit < RS_BITS ? end_bit - bit : RS_BITS;
-        const uint32_t mask = (1u << nb) - 1u;
-        const uint32_t* kin = cur ? keys_b : keys_a; const uint32_t* vin = cur ? vals_b : vals_a;
-        uint32_t* kout = cur ? keys_a : keys_b; uint32_t* vout = cur ? vals_a : vals_b;
-        hipLaunchKernelGGL((os_pass_fat_kernel<true, FT_IPT>), dim3(ft_nblocks(cap)), dim3(FT_THREADS), 0, s, kin, vin, kout, vout, (uint32_t)cap, bit, mask,
+    for (int p = 0; p < plan.count(); p++) {
+        const SortPass ps = plan.pass(p);
+        hipLaunchKernelGGL(os_pass_fat_kernel<true>, dim3(ft_nblocks(cap)), dim3(FT_THREADS), 0, s, ps.kin, ps.vin, ps.kout, ps.vout, (uint32_t)cap, ps.bit, ps.mask,
                            ghist + (size_t)p * RS_RADIX * BE_HSTRIDE, status + (size_t)p * nblocks * RS_RADIX, ticket + p, n_dev, BE_HSTRIDE,
-                           p == passes - 1 ? ranges : (uint2*)nullptr, 0u);      // (the last pass leaves the tile ranges behind, start complemented)
-        cur ^= 1;
+                           p == plan.count() - 1 ? ranges : (uint2*)nullptr, 0u);      // (the last pass leaves the tile ranges behind, start complemented)
     }
-    return cur;
+    return plan.result();
 }
-bool capacity_binning_ok(size_t cap, int end_bit) { return rs_onesweep(cap) && radix_sort_passes(cap, 0, end_bit) <= 2 && g_large_sort_impl != 3; }
-size_t bin_emit_sort_status_words(size_t cap, int end_bit) { return (size_t)radix_sort_passes(cap, 0, end_bit) * rs_nblocks(cap) * RS_RADIX; }
+bool capacity_binning_ok(size_t cap, int end_bit) { return rs_lookback(cap) && sort_passes(0, end_bit) <= 2 && g_large_sort_impl != 3; }
+size_t bin_emit_sort_status_words(size_t cap, int end_bit) { return (size_t)sort_passes(0, end_bit) * hist_nblocks(cap) * RS_RADIX; }
 size_t capacity_sort_scratch_bytes(size_t cap, int end_bit) { return (bin_emit_head_words() + bin_emit_sort_status_words(cap, end_bit)) * sizeof(uint32_t) + 256; }
 
 void launch_bin_emit(int P, const uint32_t* tiles_touched, const uint32_t* rects, const uint32_t* block_totals, float* rec, uint32_t* keys, uint32_t* vals,
@@ -886,7 +852,7 @@ void launch_bin_emit(int P, const uint32_t* tiles_touched, const uint32_t* rects
     uint32_t* ghist = static_cast<uint32_t*>(sort_scratch);
     hipLaunchKernelGGL(bin_emit_kernel, dim3((unsigned)((P + BE_THREADS - 1) / BE_THREADS)), dim3(BE_THREADS), 0, s, P, tiles_touched, rects, block_totals,
                        (uint32_t)((P + 255) / 256), rec, keys, vals, gx, (uint32_t)cap, ghist, ghist + bin_emit_head_words(), (uint32_t)bin_emit_sort_status_words(cap, end_bit),
-                       radix_sort_passes(cap, 0, end_bit), end_bit, n_out, n_host);
+                       sort_passes(0, end_bit), end_bit, n_out, n_host);
 }
 
 }  // namespace surfel

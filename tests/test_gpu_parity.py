@@ -1086,11 +1086,14 @@ def test_blend_stats_counters():
 
 @pytest.mark.parametrize("n,bits", [(1, (0, 32)), (63, (0, 32)), (2047, (0, 12)), (2048, (0, 32)), (2049, (3, 17)), (300_000, (0, 32)),
                                     (611_573, (0, 12)), (3_000_001, (0, 32)), (5_000_000, (0, 15)), (2_000_003, (7, 8)), (2_000_003, (5, 5)),
-                                    (4097, (31, 32)), (4097, (0, 0)), (8191, (0, 32)), (8193, (0, 12)), (40_000, (0, 12)), (1_048_576, (0, 13))])
+                                    (4097, (31, 32)), (4097, (0, 0)), (8191, (0, 32)), (8193, (0, 12)), (40_000, (0, 12)), (1_048_576, (0, 13)),
+                                    (4095, (0, 32)), (4096, (0, 12)), (1_048_577, (0, 9))])
 def test_radix_sort_is_stable_and_exact(n, bits):
-    """The one-launch-per-pass radix sort (decoupled look-back, 8192-item tiles staged through LDS) against
-    numpy's stable argsort, incl. heavy duplicates; 1-bit and empty key fields (the order is then the input order); large inputs
-    also through rocprim::radix_sort_pairs."""
+    """The radix sort of (key, value) pairs — 8 bits per pass, 4096-item tiles (1024 threads x 4) staged through LDS; up to 2^20 items
+    one launch per pass with decoupled look-back, above that histogram + scan + scatter per pass — against numpy's stable argsort,
+    incl. heavy duplicates; 1-bit and empty key fields (the order is then the input order); every size also through
+    rocprim::radix_sort_pairs.  4095 / 4096 / 4097 and 8191 / 8193 straddle one and two tiles, 1 048 576 / 1 048 577 the two paths
+    (the latter with two passes, one of a single bit)."""
     import torch
     import surfel_native as nat
     lib = nat.load()
