@@ -8,9 +8,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/surfel_contrib.h"
 #include "../../include/surfel_debug.h"
 #include "carve.h"
 #include "surfel_common.h"
+#include "surfel_contrib_kernel.h"
 #include "surfel_kernels.h"
 #include "train_kernels.h"
 
@@ -820,6 +822,44 @@ int surfel_knn_dist2(surfel_alloc_fn scratch_alloc, void* scratch_user, int P, c
     void* scratch = scratch_alloc(scratch_user, bytes);
     if (!scratch) return fail(SURFEL_E_ALLOC, "knn scratch allocation failed");
     launch_knn(P, points, mean_dist2, scratch, bytes, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int surfel_rasterize_contribution(int P, int64_t R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                                  const void* image_buffer, uint32_t view_tag, uint64_t* sum_q, uint64_t* hits, uint32_t* max_bits,
+                                  uint32_t* dominant, uint32_t* views, uint32_t* stamp, int32_t* dominant_id, int debug, void* stream) {
+    (void)debug;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P < 0 || R < 0 || R >= ((int64_t)1 << 32) || width <= 0 || height <= 0) return fail(SURFEL_E_INVALID, "bad sizes");
+    if (view_tag == 0u) return fail(SURFEL_E_INVALID, "view_tag must be >= 1");
+    if (P == 0 || R == 0) return 0;
+    if (!geom_buffer || !binning_buffer || !image_buffer) return fail(SURFEL_E_INVALID, "buffer is NULL");
+    if (!sum_q || !hits || !max_bits || !dominant || !views || !stamp) return fail(SURFEL_E_INVALID, "accumulator pointer is NULL");
+    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+    if (gx > 1023 || gy > 1023) return fail(SURFEL_E_LIMIT, "image larger than 16368 px per side");
+
+    GeomState geom = GeomState::carve(const_cast<void*>(geom_buffer), P, 0, nullptr);
+    BinState bin = BinState::carve(const_cast<void*>(binning_buffer), (size_t)R, 0, nullptr);
+    ImgState img = ImgState::carve(const_cast<void*>(image_buffer), width, height, nullptr);
+
+    // The capacity path leaves the frame's instance total on the device (bin_emit_kernel), the exact path leaves 0 there: R of a
+    // capacity frame may be its capacity (lazily counted) and its lists may be truncated — refused, not guessed at.
+    uint32_t n_dev = 0;
+    HIP_TRY(hipMemcpyAsync(&n_dev, img.total + 2 * R_SLOTS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_dev != 0u)
+        return fail(SURFEL_E_INVALID, "the frame was binned with a capacity (lazily counted?): render it with SURFEL_OPT_EXACT_BINNING for the contribution pass");
+
+    ContribArgs ca{};
+    ca.W = width; ca.H = height; ca.gx = gx; ca.gy = gy;
+    ca.ranges = img.ranges; ca.point_list = bin.point_list; ca.rec = geom.rec;
+    ca.tile_map = img.tile_map; ca.map_flag = img.total + 2 * R_SLOTS + 1; ca.map_len = tile_map_len(gx, gy);      // the forward's tile order
+    ca.view_tag = view_tag;
+    ca.sum_q = reinterpret_cast<unsigned long long*>(sum_q); ca.hits = reinterpret_cast<unsigned long long*>(hits);
+    ca.max_bits = max_bits; ca.dominant = dominant; ca.views = views; ca.stamp = stamp; ca.dominant_id = dominant_id;
+    ca.stats = g_blend_stats;
+    launch_contrib(ca, s);
     HIP_TRY(hipGetLastError());
     return 0;
 }

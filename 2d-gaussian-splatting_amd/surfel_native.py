@@ -104,6 +104,9 @@ SIGNATURES = {
         "surfel_set_backward_hook": (_i, HOOK_FN, _u),
         "surfel_forward_count": (_i64,),
     },
+    "surfel_contrib.h": {
+        "surfel_rasterize_contribution": (_i, _i, _i64, _i, _i, _d, _d, _d, C.c_uint32, _d, _d, _d, _d, _d, _d, _d, _i, _s),
+    },
     "surfel_debug.h": {
         "surfel_last_stage_ms": (_i, _fp, _i),
         "surfel_last_stage_ids": (_i, _ip, _i),
@@ -260,6 +263,7 @@ SIGNATURES = {
     },
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
+CONTRIB_EXPORTS = list(SIGNATURES["surfel_contrib.h"])
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
 UNBOUNDED_EXPORTS = list(SIGNATURES["surfel_mesh_unbounded.h"])
 EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])

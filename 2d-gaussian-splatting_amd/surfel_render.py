@@ -243,6 +243,23 @@ def rasterize_manual_backward(ctx, grad_image, grad_allmap):
     return _RasterizeGaussians.backward(ctx, grad_image, None, grad_allmap)[1]
 
 
+def rasterize_buffers(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, debug_bits=0):
+    """rasterize() without a gradient that also hands out the forward's state, for the passes that run on it (surfel_prune: the
+    contribution pass): returns (image, radii, allmap, buffers) with buffers = dict(geom, binning, image: the three uint8 tensors of
+    the allocator callbacks, num_rendered, P, width, height).  Native homography only."""
+    from diff_surfel_rasterization import _RasterizeGaussians
+    rs = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, debug_bits | _n.OPT_NO_STREAM)
+    ctx = _n.ManualCtx()
+    with torch.no_grad():
+        means3D = pc.get_xyz
+        none = means3D.new_empty(0)
+        shs, colors = (pc.get_features, none) if override_color is None else (none, override_color)
+        image, radii, allmap = _RasterizeGaussians.forward(ctx, means3D, none, shs, colors, pc.get_opacity, pc.get_scaling, pc.get_rotation, none, rs)
+    geom, binning, img = ctx.saved_tensors[7:10]
+    return image, radii, allmap, dict(geom=geom, binning=binning, image=img, num_rendered=ctx.num_rendered, P=ctx.dims[0],
+                                      width=ctx.dims[3], height=ctx.dims[2])
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):
     """Render the scene; background tensor must be on the GPU.  Same dict as the reference's render()."""
     image, radii, allmap, means2D = rasterize(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color)

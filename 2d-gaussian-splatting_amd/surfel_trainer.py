@@ -139,7 +139,7 @@ def capture_views(gt_model, cams, background, pipe=None):
 # ------------------------------------------------------------------------------------------------ the loop
 class Trainer:
     def __init__(self, model, cams, opt=None, pipe=None, white_background=False, extent=None, seed=0, sharding="views", first_iter=0,
-                 rehearse_exchange=False, solo=False, logger=None):
+                 rehearse_exchange=False, solo=False, logger=None, prune_at=(), prune_min_max_weight=None, prune_min_views=None):
         """sharding (N > 1): "views" = every rank trains on its own view per step (default, BASELINE config 4); "bands" = all ranks
         render row bands of the SAME view (tile-band sharding, BASELINE config 5): every rank evaluates the loss on ITS band plus a
         32-row halo received from its two neighbours (surfel_losses.train_loss_band), back-propagates its own rows, and the
@@ -151,7 +151,11 @@ class Trainer:
         solo: ignore an initialised process group — this rank trains alone (bench.py: every rank prepares the same trained state by
         itself, deterministically, before the timed view-parallel Trainer synchronises the replicas).
         logger: a surfel_log.EventWriter (LOG.md): rank 0 appends every step's scalars to it with one launch behind the step's work; None
-        (the default): no launch, no buffer, no thread."""
+        (the default): no launch, no buffer, no thread.
+        prune_at: iterations after which the model is pruned by blend contribution (CONTRIB.md, "prune and recover"): a contribution pass
+        over the training cameras, then the surfels whose largest blend weight stays below prune_min_max_weight or that fewer than
+        prune_min_views views saw are removed, behind the iteration's own densification if it has one.  Empty (the default): no launch,
+        no allocation, the same training bits.  One GPU only."""
         if sharding not in ("views", "bands"):
             raise ValueError("sharding must be 'views' or 'bands'")
         self.sharding = sharding
@@ -169,6 +173,11 @@ class Trainer:
         self.iteration = int(first_iter)      # resume: the checkpoint's iteration (train.py:37-39), so that the lr / SH / densify schedules continue
         self.last = {}
         self.logger = logger
+        self.prune_at = frozenset(int(i) for i in (prune_at or ()))
+        self.prune_rules = dict(min_max_weight=prune_min_max_weight, min_views=prune_min_views)
+        self.pruned = []                # [(iteration, surfels before, surfels after)]
+        if self.prune_at and prune_min_max_weight is None and prune_min_views is None:
+            raise ValueError("prune_at needs prune_min_max_weight or prune_min_views")
         self._lambdas = (0.0, 0.0)
         self._epoch, self._epoch_views, self._epoch_campos, self._centers = -1, None, None, None
         self._one = torch.ones((), dtype=torch.float32, device=model.device)
@@ -202,6 +211,8 @@ class Trainer:
         if model.grad is None:
             model.training_setup(self.opt)
         if self.world > 1:
+            if self.prune_at:
+                raise ValueError("prune_at is a single-GPU option")
             self._sync_replicas()
 
     def _sync_replicas(self):
@@ -260,10 +271,22 @@ class Trainer:
                 self._step_band(it, cam, lam_n, lam_d)
             else:
                 self._step_view(it, cam, lam_n, lam_d)
+        if self.prune_at and self.iteration in self.prune_at:
+            self._prune_by_contribution()
         if self.logger is not None and self.rank == 0:
             # the step's work is queued: the deferred loss scalars are valid on the stream, and `points` is the count the step rendered
             # (training_report runs before the densification, train.py:119-132)
             self.logger.append(self.iteration, self.last["points"], self.last["scalars"], *self._lambdas)
+
+    def _prune_by_contribution(self):
+        """prune_at: behind the iteration (and its densification, if it had one) — never inside it."""
+        import surfel_prune
+        m = self.model
+        with torch.no_grad():
+            c = surfel_prune.contribution(m, self.cams, self.pipe, self.background)
+            before = m.P
+            surfel_prune.prune_model(m, surfel_prune.prune_mask(c, **self.prune_rules))
+        self.pruned.append((self.iteration, before, m.P))
 
     def _begin_step(self):
         """Advance the iteration, set its learning rate and SH degree; returns (iteration, lambda_normal, lambda_dist)."""
@@ -650,6 +673,11 @@ def parse_args(argv=None):
     ap.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[])
     ap.add_argument("--start_checkpoint", type=str, default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--prune_at", nargs="+", type=int, default=[], help="prune the model by blend contribution after these iterations and train on "
+                    "(CONTRIB.md); needs --prune_min_max_weight or --prune_min_views.  Default: never")
+    ap.add_argument("--prune_min_max_weight", type=float, default=None, help="--prune_at keeps the surfels whose largest blend weight over the training "
+                    "views reaches this")
+    ap.add_argument("--prune_min_views", type=int, default=None, help="--prune_at keeps the surfels that at least this many training views saw")
     ap.add_argument("--workers", type=int, default=4, help="image decoding threads (at most 8)")
     ap.add_argument("--decode", default="host", choices=["host", "device"], help="who decodes the capture's JPEG files: Pillow on the host threads "
                     "(the default) or the decoder on the device (JPEGDEC.md); the same cameras")
@@ -734,7 +762,7 @@ def main(argv=None):
         model.restore(model_params, opt)
     logger = make_logger(vargs, args.model_path)
     tr = Trainer(model, scene.getTrainCameras(), opt, pipe, args.white_background, extent=scene.cameras_extent, seed=args.seed, first_iter=first_iter,
-                 logger=logger)
+                 logger=logger, prune_at=args.prune_at, prune_min_max_weight=args.prune_min_max_weight, prune_min_views=args.prune_min_views)
     train_cams = scene.getTrainCameras()
     reports = (("test", scene.getTestCameras()), ("train", [train_cams[i % len(train_cams)] for i in range(5, 30, 5)]))
     viewer = make_viewer(vargs)

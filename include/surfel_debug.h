@@ -38,7 +38,8 @@ int surfel_debug_set_tile_radix_min(int longest_network_run);
 
 /* A device buffer of 8 uint64 (caller-zeroed) that every following blend-backward launch accumulates into — [0] lane slots issued,
  * [1] lanes that held a composited pair, [2] wave visits, [3] (sub-tile | quad, instance) visits, [4] of those with a composited pair,
- * [5] quad variant: 4x4 sub-tiles with a composited pair — or NULL to switch the instrumented kernels off. */
+ * [5] quad variant: 4x4 sub-tiles with a composited pair; the blend forward adds [6] composited pairs, the contribution pass
+ * (surfel_contrib.h) [7] global atomics issued — or NULL to switch the instrumented kernels off. */
 int surfel_debug_set_blend_stats(void* dev_u64x8);
 
 /* How the last forward of this thread sized its binning buffers: 0 exact, 1 capacity, 2 capacity overflowed and redone, 4 lazy count. */
