@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsurfel_hip.so")
-SOURCES = ["surfel_preprocess.hip", "surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_contrib.hip", "surfel_sort.hip", "surfel_api.hip", "knn.hip", "box_probe.hip",
+SOURCES = ["surfel_preprocess.hip", "surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_contrib.hip", "surfel_select.hip", "surfel_sort.hip", "surfel_api.hip", "knn.hip", "box_probe.hip",
            "train_loss.hip", "train_post.hip", "train_fused.hip", "train_optim.hip", "train_api.hip",
            "device_scan.hip", "mesh_tsdf.hip", "mesh_unbounded.hip", "eval_geometry.hip", "eval_tnt.hip", "metrics_lpips.hip", "scene_image.hip", "frame_vis.hip", "view_image.hip", "mesh_cull.hip", "mesh_view.hip", "frame_jpeg.hip", "frame_png.hip", "scene_jpeg.hip", "scene_undistort.hip", "train_log.hip", "log_events.cpp", "mesh_simplify.hip", "mesh_texture.hip", "mesh_smooth.hip", "mesh_repair.hip"]
 # blend kernels: packed-f32 VALU (SLP) costs ~1.6x a scalar op on gfx950 plus the v_movs that pair the operands
@@ -19,6 +19,8 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          "surfel_backward_scan.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
          # surfel_contrib.hip walks as blend_fwd does and must round w = alpha * T and the transmittance as it does: the forward's flags
          "surfel_contrib.hip": ["-fno-slp-vectorize"],
+         # surfel_select.hip walks as surfel_contrib.hip does, for the same reason: the forward's flags
+         "surfel_select.hip": ["-fno-slp-vectorize"],
          # mesh_tsdf.hip: no contraction, so the allocation pass rounds as its fp32 restatement (tests/mesh_oracle.py)
          "mesh_tsdf.hip": ["-ffp-contract=off"],
          # eval_geometry.hip: no contraction, so the sampling decisions (fp64) and the thinning's pair test (fp32) round as their
@@ -62,7 +64,7 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          # mesh_repair.hip: no contraction, so a fill centroid's fp64 sum and division round as their restatement
          # (tests/repair_oracle.py) and the repaired vertices come out bit for bit
          "mesh_repair.hip": ["-ffp-contract=off"]}
-HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_contrib_kernel.h", os.path.join("..", "..", "include", "surfel_contrib.h"), "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
+HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_contrib_kernel.h", os.path.join("..", "..", "include", "surfel_contrib.h"), "surfel_select_kernel.h", os.path.join("..", "..", "include", "surfel_select.h"), "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
            os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", "mesh_mc.h", "block_ops.h", "side_util.h", "carve.h", "mesh_topology.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
            os.path.join("..", "..", "include", "surfel_mesh_unbounded.h"), os.path.join("..", "..", "include", "surfel_eval.h"),
            os.path.join("..", "..", "include", "surfel_eval_tnt.h"), os.path.join("..", "..", "include", "surfel_metrics.h"),

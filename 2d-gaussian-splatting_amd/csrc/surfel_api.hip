@@ -10,10 +10,12 @@
 
 #include "../../include/surfel_contrib.h"
 #include "../../include/surfel_debug.h"
+#include "../../include/surfel_select.h"
 #include "carve.h"
 #include "surfel_common.h"
 #include "surfel_contrib_kernel.h"
 #include "surfel_kernels.h"
+#include "surfel_select_kernel.h"
 #include "train_kernels.h"
 
 using namespace surfel;
@@ -860,6 +862,43 @@ int surfel_rasterize_contribution(int P, int64_t R, int width, int height, const
     ca.max_bits = max_bits; ca.dominant = dominant; ca.views = views; ca.stamp = stamp; ca.dominant_id = dominant_id;
     ca.stats = g_blend_stats;
     launch_contrib(ca, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int surfel_rasterize_label_votes(int P, int64_t R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                                 const void* image_buffer, const uint8_t* labels, int num_labels, uint64_t* votes, int debug,
+                                 void* stream) {
+    (void)debug;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P < 0 || R < 0 || R >= ((int64_t)1 << 32) || width <= 0 || height <= 0) return fail(SURFEL_E_INVALID, "bad sizes");
+    if (num_labels < 1 || num_labels > SURFEL_SELECT_MAX_LABELS) return fail(SURFEL_E_INVALID, "num_labels must be in 1 .. 32");
+    if (P == 0 || R == 0) return 0;
+    if (!geom_buffer || !binning_buffer || !image_buffer) return fail(SURFEL_E_INVALID, "buffer is NULL");
+    if (!labels) return fail(SURFEL_E_INVALID, "labels pointer is NULL");
+    if (!votes) return fail(SURFEL_E_INVALID, "votes pointer is NULL");
+    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+    if (gx > 1023 || gy > 1023) return fail(SURFEL_E_LIMIT, "image larger than 16368 px per side");
+
+    GeomState geom = GeomState::carve(const_cast<void*>(geom_buffer), P, 0, nullptr);
+    BinState bin = BinState::carve(const_cast<void*>(binning_buffer), (size_t)R, 0, nullptr);
+    ImgState img = ImgState::carve(const_cast<void*>(image_buffer), width, height, nullptr);
+
+    // as surfel_rasterize_contribution: the capacity path leaves the frame's instance total on the device, the exact path leaves 0
+    uint32_t n_dev = 0;
+    HIP_TRY(hipMemcpyAsync(&n_dev, img.total + 2 * R_SLOTS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_dev != 0u)
+        return fail(SURFEL_E_INVALID, "the frame was binned with a capacity (lazily counted?): render it with SURFEL_OPT_EXACT_BINNING for the label pass");
+
+    SelectArgs sa{};
+    sa.W = width; sa.H = height; sa.gx = gx; sa.gy = gy;
+    sa.ranges = img.ranges; sa.point_list = bin.point_list; sa.rec = geom.rec;
+    sa.tile_map = img.tile_map; sa.map_flag = img.total + 2 * R_SLOTS + 1; sa.map_len = tile_map_len(gx, gy);      // the forward's tile order
+    sa.labels = labels; sa.K = num_labels;
+    sa.votes = reinterpret_cast<unsigned long long*>(votes);
+    sa.stats = g_blend_stats;
+    launch_select(sa, s);
     HIP_TRY(hipGetLastError());
     return 0;
 }

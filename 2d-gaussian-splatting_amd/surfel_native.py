@@ -107,6 +107,9 @@ SIGNATURES = {
     "surfel_contrib.h": {
         "surfel_rasterize_contribution": (_i, _i, _i64, _i, _i, _d, _d, _d, C.c_uint32, _d, _d, _d, _d, _d, _d, _d, _i, _s),
     },
+    "surfel_select.h": {
+        "surfel_rasterize_label_votes": (_i, _i, _i64, _i, _i, _d, _d, _d, _d, _i, _d, _i, _s),
+    },
     "surfel_debug.h": {
         "surfel_last_stage_ms": (_i, _fp, _i),
         "surfel_last_stage_ids": (_i, _ip, _i),
@@ -264,6 +267,7 @@ SIGNATURES = {
 }
 EXPORTS = [name for h in ("surfel_hip.h", "surfel_debug.h", "surfel_train.h") for name in SIGNATURES[h]]
 CONTRIB_EXPORTS = list(SIGNATURES["surfel_contrib.h"])
+SELECT_EXPORTS = list(SIGNATURES["surfel_select.h"])
 MESH_EXPORTS = list(SIGNATURES["surfel_mesh.h"])
 UNBOUNDED_EXPORTS = list(SIGNATURES["surfel_mesh_unbounded.h"])
 EVAL_EXPORTS = list(SIGNATURES["surfel_eval.h"])
