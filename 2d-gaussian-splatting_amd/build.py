@@ -64,7 +64,7 @@ EXTRA = {"surfel_forward.hip": ["-fno-slp-vectorize"], "surfel_backward.hip": ["
          # mesh_repair.hip: no contraction, so a fill centroid's fp64 sum and division round as their restatement
          # (tests/repair_oracle.py) and the repaired vertices come out bit for bit
          "mesh_repair.hip": ["-ffp-contract=off"]}
-HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_contrib_kernel.h", os.path.join("..", "..", "include", "surfel_contrib.h"), "surfel_select_kernel.h", os.path.join("..", "..", "include", "surfel_select.h"), "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
+HEADERS = ["surfel_common.h", "surfel_kernels.h", "surfel_tile_walk.h", "surfel_contrib_kernel.h", os.path.join("..", "..", "include", "surfel_contrib.h"), "surfel_select_kernel.h", os.path.join("..", "..", "include", "surfel_select.h"), "surfel_blend_bwd.h", "train_kernels.h", "train_loss_body.h", "train_post_body.h", os.path.join("..", "..", "include", "surfel_hip.h"), os.path.join("..", "..", "include", "surfel_debug.h"),
            os.path.join("..", "..", "include", "surfel_train.h"), "mesh_mc_table.h", "mesh_mc.h", "block_ops.h", "side_util.h", "carve.h", "mesh_topology.h", os.path.join("..", "..", "include", "surfel_mesh.h"),
            os.path.join("..", "..", "include", "surfel_mesh_unbounded.h"), os.path.join("..", "..", "include", "surfel_eval.h"),
            os.path.join("..", "..", "include", "surfel_eval_tnt.h"), os.path.join("..", "..", "include", "surfel_metrics.h"),

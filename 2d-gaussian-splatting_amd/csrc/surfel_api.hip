@@ -828,16 +828,20 @@ int surfel_knn_dist2(surfel_alloc_fn scratch_alloc, void* scratch_user, int P, c
     return 0;
 }
 
-int surfel_rasterize_contribution(int P, int64_t R, int width, int height, const void* geom_buffer, const void* binning_buffer,
-                                  const void* image_buffer, uint32_t view_tag, uint64_t* sum_q, uint64_t* hits, uint32_t* max_bits,
-                                  uint32_t* dominant, uint32_t* views, uint32_t* stamp, int32_t* dominant_id, int debug, void* stream) {
-    (void)debug;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// What the passes that run behind a forward (surfel_tile_walk.h) share: the checks of the frame's sizes and buffers, and the frame.
+// pass: the caller's name in the refusal of a capacity-binned frame.  bad_arg, null_ptr: the caller's complaint about its own scalar
+// arguments and about its own pointers (NULL: none), reported where they always were — behind the sizes, and behind the buffers but
+// before the device is touched.  empty: P == 0 or R == 0 — the entry returns 0 without a launch; no pointer was looked at.
+static int walk_frame(const char* pass, const char* bad_arg, const char* null_ptr, int P, int64_t R, int width, int height,
+                      const void* geom_buffer, const void* binning_buffer, const void* image_buffer, hipStream_t s, WalkFrame& out,
+                      bool& empty) {
+    empty = false;
     if (P < 0 || R < 0 || R >= ((int64_t)1 << 32) || width <= 0 || height <= 0) return fail(SURFEL_E_INVALID, "bad sizes");
-    if (view_tag == 0u) return fail(SURFEL_E_INVALID, "view_tag must be >= 1");
-    if (P == 0 || R == 0) return 0;
+    if (bad_arg) return fail(SURFEL_E_INVALID, bad_arg);
+    empty = P == 0 || R == 0;
+    if (empty) return 0;
     if (!geom_buffer || !binning_buffer || !image_buffer) return fail(SURFEL_E_INVALID, "buffer is NULL");
-    if (!sum_q || !hits || !max_bits || !dominant || !views || !stamp) return fail(SURFEL_E_INVALID, "accumulator pointer is NULL");
+    if (null_ptr) return fail(SURFEL_E_INVALID, null_ptr);
     const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
     if (gx > 1023 || gy > 1023) return fail(SURFEL_E_LIMIT, "image larger than 16368 px per side");
 
@@ -850,13 +854,27 @@ int surfel_rasterize_contribution(int P, int64_t R, int width, int height, const
     uint32_t n_dev = 0;
     HIP_TRY(hipMemcpyAsync(&n_dev, img.total + 2 * R_SLOTS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (n_dev != 0u)
-        return fail(SURFEL_E_INVALID, "the frame was binned with a capacity (lazily counted?): render it with SURFEL_OPT_EXACT_BINNING for the contribution pass");
+    if (n_dev != 0u) {
+        const std::string what = std::string("the frame was binned with a capacity (lazily counted?): render it with SURFEL_OPT_EXACT_BINNING for the ") + pass + " pass";
+        return fail(SURFEL_E_INVALID, what.c_str());
+    }
+    out.W = width; out.H = height; out.gx = gx; out.gy = gy;
+    out.ranges = img.ranges; out.point_list = bin.point_list; out.rec = geom.rec;
+    out.tile_map = img.tile_map; out.map_flag = img.total + 2 * R_SLOTS + 1; out.map_len = tile_map_len(gx, gy);      // the forward's tile order
+    return 0;
+}
 
+int surfel_rasterize_contribution(int P, int64_t R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                                  const void* image_buffer, uint32_t view_tag, uint64_t* sum_q, uint64_t* hits, uint32_t* max_bits,
+                                  uint32_t* dominant, uint32_t* views, uint32_t* stamp, int32_t* dominant_id, int debug, void* stream) {
+    (void)debug;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     ContribArgs ca{};
-    ca.W = width; ca.H = height; ca.gx = gx; ca.gy = gy;
-    ca.ranges = img.ranges; ca.point_list = bin.point_list; ca.rec = geom.rec;
-    ca.tile_map = img.tile_map; ca.map_flag = img.total + 2 * R_SLOTS + 1; ca.map_len = tile_map_len(gx, gy);      // the forward's tile order
+    bool empty;
+    const int e = walk_frame("contribution", view_tag == 0u ? "view_tag must be >= 1" : nullptr,
+                             !sum_q || !hits || !max_bits || !dominant || !views || !stamp ? "accumulator pointer is NULL" : nullptr, P, R, width, height,
+                             geom_buffer, binning_buffer, image_buffer, s, ca.frame, empty);
+    if (e || empty) return e;
     ca.view_tag = view_tag;
     ca.sum_q = reinterpret_cast<unsigned long long*>(sum_q); ca.hits = reinterpret_cast<unsigned long long*>(hits);
     ca.max_bits = max_bits; ca.dominant = dominant; ca.views = views; ca.stamp = stamp; ca.dominant_id = dominant_id;
@@ -871,30 +889,12 @@ int surfel_rasterize_label_votes(int P, int64_t R, int width, int height, const 
                                  void* stream) {
     (void)debug;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P < 0 || R < 0 || R >= ((int64_t)1 << 32) || width <= 0 || height <= 0) return fail(SURFEL_E_INVALID, "bad sizes");
-    if (num_labels < 1 || num_labels > SURFEL_SELECT_MAX_LABELS) return fail(SURFEL_E_INVALID, "num_labels must be in 1 .. 32");
-    if (P == 0 || R == 0) return 0;
-    if (!geom_buffer || !binning_buffer || !image_buffer) return fail(SURFEL_E_INVALID, "buffer is NULL");
-    if (!labels) return fail(SURFEL_E_INVALID, "labels pointer is NULL");
-    if (!votes) return fail(SURFEL_E_INVALID, "votes pointer is NULL");
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    if (gx > 1023 || gy > 1023) return fail(SURFEL_E_LIMIT, "image larger than 16368 px per side");
-
-    GeomState geom = GeomState::carve(const_cast<void*>(geom_buffer), P, 0, nullptr);
-    BinState bin = BinState::carve(const_cast<void*>(binning_buffer), (size_t)R, 0, nullptr);
-    ImgState img = ImgState::carve(const_cast<void*>(image_buffer), width, height, nullptr);
-
-    // as surfel_rasterize_contribution: the capacity path leaves the frame's instance total on the device, the exact path leaves 0
-    uint32_t n_dev = 0;
-    HIP_TRY(hipMemcpyAsync(&n_dev, img.total + 2 * R_SLOTS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (n_dev != 0u)
-        return fail(SURFEL_E_INVALID, "the frame was binned with a capacity (lazily counted?): render it with SURFEL_OPT_EXACT_BINNING for the label pass");
-
     SelectArgs sa{};
-    sa.W = width; sa.H = height; sa.gx = gx; sa.gy = gy;
-    sa.ranges = img.ranges; sa.point_list = bin.point_list; sa.rec = geom.rec;
-    sa.tile_map = img.tile_map; sa.map_flag = img.total + 2 * R_SLOTS + 1; sa.map_len = tile_map_len(gx, gy);      // the forward's tile order
+    bool empty;
+    const int e = walk_frame("label", num_labels < 1 || num_labels > SURFEL_SELECT_MAX_LABELS ? "num_labels must be in 1 .. 32" : nullptr,
+                             !labels ? "labels pointer is NULL" : !votes ? "votes pointer is NULL" : nullptr, P, R, width, height,
+                             geom_buffer, binning_buffer, image_buffer, s, sa.frame, empty);
+    if (e || empty) return e;
     sa.labels = labels; sa.K = num_labels;
     sa.votes = reinterpret_cast<unsigned long long*>(votes);
     sa.stats = g_blend_stats;

@@ -2,13 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "surfel_tile_walk.h"
 
 namespace surfel {
 
 struct ContribArgs {
-    int W, H, gx, gy;
-    const uint2* ranges; const uint32_t* point_list; const float* rec;      // the forward's tile lists and surfel records
-    const int* tile_map; const uint32_t* map_flag; int map_len;             // as BlendFwdArgs: the forward's tile order, the grid size
+    WalkFrame frame;                                                        // the forward's buffers
     uint32_t view_tag;                                                      // >= 1, rising from call to call for one accumulator set
     unsigned long long* sum_q; unsigned long long* hits;                    // [P] += rint(w 2^24) | += 1 per composited pair
     uint32_t* max_bits; uint32_t* dominant; uint32_t* views; uint32_t* stamp;      // [P] max of w's bits | += pixels dominated | += 1 per view | last tag seen

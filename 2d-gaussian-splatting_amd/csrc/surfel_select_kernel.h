@@ -2,15 +2,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "surfel_tile_walk.h"
 
 namespace surfel {
 
 constexpr int SELECT_MAX_LABELS = 32;
 
 struct SelectArgs {
-    int W, H, gx, gy;
-    const uint2* ranges; const uint32_t* point_list; const float* rec;      // the forward's tile lists and surfel records
-    const int* tile_map; const uint32_t* map_flag; int map_len;             // as ContribArgs: the forward's tile order, the grid size
+    WalkFrame frame;                                                        // the forward's buffers
     const uint8_t* labels;                                                  // [H, W]: the pixel's label; >= K = ignored
     int K;                                                                  // 1 .. SELECT_MAX_LABELS
     unsigned long long* votes;                                              // [P, K] += rint(w 2^24) of the pairs composited at pixels of label k

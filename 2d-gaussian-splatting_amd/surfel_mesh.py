@@ -472,6 +472,25 @@ def _scene_cameras(args, gaussians, it):
     return scene.getTrainCameras(), scene.getTestCameras()
 
 
+def open_model(args, device):
+    """What the tools that run a pass over a trained model's views open (surfel_prune.py, surfel_select.py), from args.model_path,
+    args.iteration (< 0: the latest), args.source_path (None: the cameras of cameras.json) and args.white_background:
+    (gaussians, cameras, iteration, the iteration's folder, pipe, background)."""
+    import surfel_io
+    import surfel_model
+    it = args.iteration if args.iteration >= 0 else _latest_iteration(args.model_path)
+    gaussians = surfel_model.GaussianModel(3, device=device)
+    folder = os.path.join(args.model_path, "point_cloud", "iteration_%d" % it)
+    if args.source_path is None:
+        gaussians.load_ply(os.path.join(folder, "point_cloud.ply"))
+        cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=device)
+    else:
+        cams, _ = _scene_cameras(args, gaussians, it)      # (loads the point cloud of iteration `it` into gaussians)
+    pipe = argparse.Namespace(depth_ratio=0.0, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
+    background = torch.tensor([1.0, 1.0, 1.0] if args.white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
+    return gaussians, cams, it, folder, pipe, background
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="TSDF mesh of a trained model (render.py's mesh step), bounded or --unbounded. Unlike the reference, which "
                                              "fuses only the training split, every camera in cameras.json is fused.  --render_path adds "

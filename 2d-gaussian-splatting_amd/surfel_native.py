@@ -464,6 +464,23 @@ def device_tensor(who, t, what=None):
     return t
 
 
+def view_buffers(who, buffers, device, P, holder):
+    """(b, W, H) of the view a pass runs behind: `buffers` is surfel_render.rasterize_buffers' dict, or a render package that carries
+    it under "buffers".  ValueError when a key is missing or the view's surfel count is not P, RuntimeError unless `device` (where the
+    pass accumulates; holder: what it accumulates in, for the messages) and the three buffers are on a HIP device."""
+    b = buffers.get("buffers", buffers)
+    for k in ("geom", "binning", "image", "num_rendered", "width", "height"):
+        if k not in b:
+            raise ValueError("%s: the view's buffers lack %r" % (who, k))
+    if device.type != "cuda":
+        raise RuntimeError("%s: tensors must live on a HIP device (the %s are on %s)" % (who, holder, device))
+    for k in ("geom", "binning", "image"):
+        device_tensor(who, b[k], k)
+    if "P" in b and int(b["P"]) != P:
+        raise ValueError("%s: the view rendered %d surfels, the %s hold %d" % (who, int(b["P"]), holder, P))
+    return b, int(b["width"]), int(b["height"])
+
+
 def uint8_buffer(who, t, n, device, what="out", at_least=False):
     """The buffer for `n` output bytes: a new uint8 [n] on `device` when the caller supplied none (t is None), otherwise t — ValueError
     unless it is a contiguous uint8 tensor of n elements (any shape) or, with at_least, a one-dimensional one of n elements or more

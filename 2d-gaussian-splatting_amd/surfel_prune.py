@@ -44,20 +44,10 @@ class Contribution:
         "buffers") — geom, binning, image, num_rendered, width, height — of a frame rendered with OPT_EXACT_BINNING.  tag: the view's
         number, >= 1 and rising from call to call (default: the next one); a tag seen before counts no view twice."""
         global launches
-        b = buffers.get("buffers", buffers)
-        for k in ("geom", "binning", "image", "num_rendered", "width", "height"):
-            if k not in b:
-                raise ValueError("%s: the view's buffers lack %r" % (WHO, k))
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: tensors must live on a HIP device (the accumulators are on %s)" % (WHO, self.device))
-        for k in ("geom", "binning", "image"):
-            _n.device_tensor(WHO, b[k], k)
-        if "P" in b and int(b["P"]) != self.P:
-            raise ValueError("%s: the view rendered %d surfels, the accumulators hold %d" % (WHO, int(b["P"]), self.P))
+        b, W, H = _n.view_buffers(WHO, buffers, self.device, self.P, "accumulators")
         tag = self.next_tag if tag is None else int(tag)
         if not 1 <= tag < 2 ** 31:
             raise ValueError("%s: tag must be in [1, 2^31)" % WHO)
-        W, H = int(b["width"]), int(b["height"])
         dom = torch.full((H, W), -1, dtype=torch.int32, device=self.device) if dominant_id else None
         _n.call(self.device, "surfel_rasterize_contribution", self.P, int(b["num_rendered"]), W, H, b["geom"], b["binning"], b["image"], tag,
                 self.sum_q, self.hits_q, self.max_bits, self.dominant_q, self.views_q, self.stamp, dom, 0)
@@ -212,20 +202,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.keep is not None and args.keep_ratio is not None:
         raise SystemExit("give --keep or --keep_ratio, not both")
-    import surfel_io
     import surfel_mesh
-    import surfel_model
-    dev = torch.device("cuda:0")
-    it = args.iteration if args.iteration >= 0 else surfel_mesh._latest_iteration(args.model_path)
-    gaussians = surfel_model.GaussianModel(3, device=dev)
-    folder = os.path.join(args.model_path, "point_cloud", "iteration_%d" % it)
-    if args.source_path is None:
-        gaussians.load_ply(os.path.join(folder, "point_cloud.ply"))
-        cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=dev)
-    else:
-        cams, _ = surfel_mesh._scene_cameras(args, gaussians, it)      # (loads the point cloud of iteration `it` into gaussians)
-    pipe = argparse.Namespace(depth_ratio=0.0, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
-    bg = torch.tensor([1.0, 1.0, 1.0] if args.white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+    gaussians, cams, it, folder, pipe, bg = surfel_mesh.open_model(args, torch.device("cuda:0"))
     c = contribution(gaussians, cams, pipe, bg)
     if args.report:
         report(c)

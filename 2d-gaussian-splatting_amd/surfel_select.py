@@ -46,24 +46,14 @@ class LabelVotes:
         "buffers": geom, binning, image, num_rendered, width, height, of a frame rendered with OPT_EXACT_BINNING) with its label image:
         a contiguous uint8 [H, W] tensor on the votes' device; a pixel whose label is >= K (by convention 255) votes for nothing."""
         global launches
-        b = buffers.get("buffers", buffers)
-        for k in ("geom", "binning", "image", "num_rendered", "width", "height"):
-            if k not in b:
-                raise ValueError("%s: the view's buffers lack %r" % (WHO, k))
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: tensors must live on a HIP device (the votes are on %s)" % (WHO, self.device))
-        for k in ("geom", "binning", "image"):
-            _n.device_tensor(WHO, b[k], k)
+        b, W, H = _n.view_buffers(WHO, buffers, self.device, self.P, "votes")
         _n.device_tensor(WHO, labels, "labels")
-        W, H = int(b["width"]), int(b["height"])
         if labels.dtype != torch.uint8:
             raise ValueError("%s: labels must be uint8, got %s" % (WHO, labels.dtype))
         if tuple(labels.shape) != (H, W):
             raise ValueError("%s: labels must be [%d, %d] (the view's height and width), got %s" % (WHO, H, W, list(labels.shape)))
         if labels.device != self.votes.device:
             raise ValueError("%s: labels live on %s, the votes on %s" % (WHO, labels.device, self.votes.device))
-        if "P" in b and int(b["P"]) != self.P:
-            raise ValueError("%s: the view rendered %d surfels, the votes hold %d" % (WHO, int(b["P"]), self.P))
         labels = labels.contiguous()
         _n.call(self.device, "surfel_rasterize_label_votes", self.P, int(b["num_rendered"]), W, H, b["geom"], b["binning"], b["image"],
                 labels, self.K, self.votes, 0)
@@ -304,26 +294,14 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if not args.report and args.keep is None and args.remove is None:
         raise SystemExit("give --keep or --remove (or --report)")
-    import surfel_io
     import surfel_mesh
-    import surfel_model
-    dev = torch.device("cuda:0")
-    it = args.iteration if args.iteration >= 0 else surfel_mesh._latest_iteration(args.model_path)
-    gaussians = surfel_model.GaussianModel(3, device=dev)
-    folder = os.path.join(args.model_path, "point_cloud", "iteration_%d" % it)
-    if args.source_path is None:
-        gaussians.load_ply(os.path.join(folder, "point_cloud.ply"))
-        cams = surfel_io.read_cameras_json(os.path.join(args.model_path, "cameras.json"), device=dev)
-    else:
-        cams, _ = surfel_mesh._scene_cameras(args, gaussians, it)      # (loads the point cloud of iteration `it` into gaussians)
+    gaussians, cams, it, folder, pipe, bg = surfel_mesh.open_model(args, torch.device("cuda:0"))
     masks, missing = load_masks(args.masks, cams, args.binary)
     if not masks:
         raise SystemExit("no mask under %s matches a camera's image name" % args.masks)
     K = args.num_labels
     if K is None:
         K = 2 if args.binary else 1 + max(int(m[m != UNLABELLED].max(initial=0)) for m in masks.values())
-    pipe = argparse.Namespace(depth_ratio=0.0, debug=0, compute_cov3D_python=False, convert_SHs_python=False)
-    bg = torch.tensor([1.0, 1.0, 1.0] if args.white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
     lv = label_votes(gaussians, cams, masks, K, pipe, bg)
     labels = assign(lv, bias=args.bias, min_share=args.min_share)
     if args.report:

@@ -215,12 +215,24 @@ def test_contrib_header_exported_and_signature_matches():
 
 
 def test_existing_rasterizer_sources_are_untouched_by_the_pass():
-    """the pass shares the walk's definitions through surfel_common.h and adds nothing to the rasterizer's own files"""
+    """the pass adds nothing to the rasterizer's own files; the walk's definitions reach it through surfel_tile_walk.h alone, which
+    takes them from surfel_common.h: no private copy of the walk in either pass"""
     csrc = os.path.join(PKG, "csrc")
     for f in ("surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_preprocess.hip", "surfel_sort.hip"):
         txt = open(os.path.join(csrc, f)).read()
-        assert "surfel_contrib" not in txt and "ContribArgs" not in txt, f
-    src = open(os.path.join(csrc, "surfel_contrib.hip")).read()
+        assert "surfel_contrib" not in txt and "ContribArgs" not in txt and "surfel_tile_walk" not in txt, f
+    walk = open(os.path.join(csrc, "surfel_tile_walk.h")).read()
     for shared in ("pair_hit(", "make_foot(", "subtile_overlap(", "thread_pixel(", "block_tile("):
-        assert shared in src, shared
+        assert shared in walk, shared
+    assert "T_EPS" in walk and '#include "surfel_common.h"' in walk
+    for f in ("surfel_contrib.hip", "surfel_select.hip"):
+        src = open(os.path.join(csrc, f)).read()
+        assert '#include "surfel_tile_walk.h"' in src and "tile_walk(" in src, f
+        for private in ("pair_hit(", "make_foot(", "subtile_overlap(", "thread_pixel(", "block_tile(", "T_EPS"):
+            assert private not in src, (f, private)
+    spec = __import__("importlib.util").util.spec_from_file_location("surfel_build_walk", os.path.join(PKG, "build.py"))
+    mod = __import__("importlib.util").util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert "surfel_tile_walk.h" in mod.HEADERS
+    src = open(os.path.join(csrc, "surfel_contrib.hip")).read()
     assert "atomicAdd(&a.sum_q" in src and "float*" not in src.split("contrib_kernel(ContribArgs a)")[1]      # integer accumulators only

@@ -43,6 +43,42 @@ def test_blend_kernels_keep_their_occupancy(src):
     assert seen == sum(1 for k in LIMITS if any(t in k for t in tags)), "a kernel of %s was renamed or is gone" % src
 
 
+# The passes on the shared tile walk (csrc/surfel_tile_walk.h), the shipped instances: kernel -> (LDS bytes, waves / SIMD).  LDS is what
+# the kernels had before the walk was shared (SELECT.md's table, confirmed from a build of that commit); the waves are that table's:
+# min(8, 512 // registers in granules of 8, workgroups / CU by LDS), the last with one wave of each workgroup on each SIMD.
+WALK_KERNELS = {
+    "contrib_kernel<false>(ContribArgs)": (16256, 8),
+    "select_kernel<2, false>(SelectArgs)": (16256, 8),
+    "select_kernel<8, false>(SelectArgs)": (22400, 7),
+    "select_kernel<32, false>(SelectArgs)": (46976, 3),
+}
+
+
+@pytest.mark.parametrize("src", ["surfel_contrib.hip", "surfel_select.hip"])
+def test_walk_passes_keep_their_registers_and_lds(src):
+    """No scratch, at most 64 VGPRs, the LDS of the kernels before they shared the walk, and the occupancy step of SELECT.md's table.
+    The VGPR count is the descriptor's accum_offset: the architected registers in granules of 4, which is the count that table gives.
+    (next_free_vgpr, which the occupancy is computed from, is larger for the kernels whose occupancy LDS bounds: there the compiler
+    raises it to the first count that admits no more waves than the LDS does — 65 for seven waves, 129 for three.)"""
+    import isa_count
+    ks = isa_count.kernels(isa_count.assemble(src))
+    seen = 0
+    for name, (lines, md) in ks.items():
+        dn = isa_count.demangle(name)
+        if dn not in WALK_KERNELS:
+            continue
+        seen += 1
+        lds, waves = WALK_KERNELS[dn]
+        assert md["private_segment_fixed_size"] == 0, "%s spills %d B to scratch" % (dn, md["private_segment_fixed_size"])
+        assert md["accum_offset"] <= 64, "%s: %d architected VGPRs (limit 64)" % (dn, md["accum_offset"])      # (not next_free_vgpr: see the docstring)
+        assert md["group_segment_fixed_size"] == lds, "%s: %d B of LDS (was %d)" % (dn, md["group_segment_fixed_size"], lds)
+        by_regs, by_lds = isa_count.occupancy(md["next_free_vgpr"], md["group_segment_fixed_size"])
+        assert min(by_regs, by_lds) >= waves, "%s: %d waves / SIMD (was %d)" % (dn, min(by_regs, by_lds), waves)
+        # the walk must still be there: an innermost loop with the per-visit arithmetic
+        assert any(d == 2 and c.get("valu", 0) >= 60 for (_h, d, _p, c, _dpp, _tr) in isa_count.loops(lines)), dn
+    assert seen == sum(1 for k in WALK_KERNELS if src[len("surfel_"):-len(".hip")] in k), "a kernel of %s was renamed or is gone" % src
+
+
 def test_loss_launches_keep_five_workgroups_per_cu():
     """Round 5 (scripts/loss_trace.hip): the fused loss launches were the sum of their workgroups' latencies over the resident slots; at
     <= 96 VGPRs and <= 32 KB of LDS five workgroups fit a CU (three before: 43 / 45 KB).  The horizontal pass keeps its results in

@@ -71,14 +71,21 @@ def test_select_source_is_built_with_the_forwards_flags_and_leaves_the_walk_alon
     mod = __import__("importlib.util").util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     assert "surfel_select.hip" in mod.SOURCES and mod.EXTRA["surfel_select.hip"] == mod.EXTRA["surfel_forward.hip"] == mod.EXTRA["surfel_contrib.hip"]
-    assert any(h.endswith(HEADER) for h in mod.HEADERS) and "surfel_select_kernel.h" in mod.HEADERS
+    assert any(h.endswith(HEADER) for h in mod.HEADERS) and "surfel_select_kernel.h" in mod.HEADERS and "surfel_tile_walk.h" in mod.HEADERS
     csrc = os.path.join(PKG, "csrc")
     for f in ("surfel_forward.hip", "surfel_backward.hip", "surfel_backward_scan.hip", "surfel_preprocess.hip", "surfel_sort.hip", "surfel_contrib.hip"):
         txt = open(os.path.join(csrc, f)).read()
         assert "surfel_select" not in txt and "SelectArgs" not in txt, f
-    src = open(os.path.join(csrc, "surfel_select.hip")).read()
+    # the walk is surfel_tile_walk.h's: its definitions occur there, and no private copy of it in either pass
+    walk = open(os.path.join(csrc, "surfel_tile_walk.h")).read()
     for shared in ("pair_hit(", "make_foot(", "subtile_overlap(", "thread_pixel(", "block_tile("):
-        assert shared in src, shared
+        assert shared in walk, shared
+    for f in ("surfel_select.hip", "surfel_contrib.hip"):
+        txt = open(os.path.join(csrc, f)).read()
+        assert '#include "surfel_tile_walk.h"' in txt and "tile_walk(" in txt, f
+        for private in ("pair_hit(", "make_foot(", "subtile_overlap(", "thread_pixel(", "block_tile(", "T_EPS"):
+            assert private not in txt, (f, private)
+    src = open(os.path.join(csrc, "surfel_select.hip")).read()
     body = src.split("select_kernel(SelectArgs a)")[1]
     assert "atomicAdd(&dst[k], (unsigned long long)v)" in body and "float*" not in body      # integer accumulators only
 
