@@ -564,6 +564,13 @@ int64_t surfel_forward_count(void) {
     return R;
 }
 
+// An SH store of M coefficients per surfel serves degree D only if (D + 1)^2 <= M: forward and backward index it by the degree.
+static int check_sh(int D, int M, const float* shs) {
+    if (D >= 0 && D <= 3 && (!shs || M >= (D + 1) * (D + 1))) return 0;
+    const std::string what = "bad SH degree / coefficient count: degree " + std::to_string(D) + ", " + std::to_string(M) + " coefficients per surfel";
+    return fail(SURFEL_E_INVALID, what.c_str());
+}
+
 int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, surfel_alloc_fn binning_alloc, void* binning_user,
                                  surfel_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background,
                                  int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -596,7 +603,7 @@ int64_t surfel_rasterize_forward(surfel_alloc_fn geom_alloc, void* geom_user, su
         if (has_sr == (transMat_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr)))
             return fail(SURFEL_E_INVALID, "provide exactly one of (scales, rotations) / transMat_precomp");
         if (!means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos || !radii) return fail(SURFEL_E_INVALID, "required pointer is NULL");
-        if (D < 0 || D > 3 || (shs && M < (D + 1) * (D + 1))) return fail(SURFEL_E_INVALID, "bad SH degree / coefficient count");
+        if (int e = check_sh(D, M, shs)) return e;
     }
     if (!background || !out_color || !out_others) return fail(SURFEL_E_INVALID, "required pointer is NULL");
     const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
@@ -726,6 +733,7 @@ int surfel_rasterize_backward(surfel_alloc_fn scratch_alloc, void* scratch_user,
         return fail(SURFEL_E_INVALID, "gradient pointer is NULL");
     if (transMat_precomp && !dL_dtransMat) return fail(SURFEL_E_INVALID, "dL_dtransMat is NULL but transMat_precomp was given");
     if (!transMat_precomp && (!dL_dscales || !dL_drots || !scales || !rotations)) return fail(SURFEL_E_INVALID, "scale/rotation pointers are NULL");
+    if (int e = check_sh(D, M, shs)) return e;
     const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
 
     GeomState geom = GeomState::carve(const_cast<void*>(geom_buffer), P, 0, nullptr);   // rocPRIM scratch is last: layout of the rest is size-independent

@@ -291,6 +291,7 @@ _SIG = {name: sig for group in SIGNATURES.values() for name, sig in group.items(
 
 
 # error codes and the per-call option overrides carried in the upper bits of the `debug` argument (include/surfel_hip.h, its order)
+E_INVALID = -1
 E_LIMIT = -4
 E_OVERFLOW = -5
 OPT_NO_CULL = 1 << 8

@@ -54,10 +54,10 @@ typedef void* (*surfel_alloc_fn)(void* user, size_t bytes);
 int surfel_abi_version(void);
 const char* surfel_last_error(void);
 /* Forward.  Replaces `_C.rasterize_gaussians` (call site /root/reference/gaussian_renderer/__init__.py:97-106).
- *   P surfels, D active SH degree (0..3), M SH coefficients stored per surfel (16).  background[3]; means3D[P,3]; shs[P,M,3] or NULL;
- *   colors_precomp[P,3] or NULL (exactly one); opacities[P]; scales[P,2] + rotations[P,4] (w,x,y,z) or transMat_precomp[P,9] (exactly
- *   one); viewmatrix[16] = world_view_transform, projmatrix[16] = full_proj_transform as torch stores them (transposed,
- *   /root/reference/scene/cameras.py:56-58); cam_pos[3].
+ *   P surfels, D active SH degree (0..3), M >= (D + 1)^2 SH coefficients stored per surfel (16; fewer is SURFEL_E_INVALID, here and in
+ *   the backward; those above the degree are never read).  background[3]; means3D[P,3]; shs[P,M,3] or NULL; colors_precomp[P,3] or NULL
+ *   (exactly one); opacities[P]; scales[P,2] + rotations[P,4] (w,x,y,z) or transMat_precomp[P,9] (exactly one); viewmatrix[16] =
+ *   world_view_transform, projmatrix[16] = full_proj_transform as torch stores them (transposed, /root/reference/scene/cameras.py:56-58); cam_pos[3].
  * Outputs (caller-allocated): out_color[3,H,W], out_others[7,H,W] (0 sum w*depth, 1 alpha, 2-4 view-space normal, 5 median depth,
  *   6 distortion: /root/reference/gaussian_renderer/__init__.py:118-135), radii[P] int32.  The three buffers obtained through the
  *   callbacks are kept by the caller and handed to surfel_rasterize_backward unchanged.

@@ -56,6 +56,7 @@ class HipRun:
                                               n.ptr(self.rots), n.ptr(self.trans), n.ptr(self.view), n.ptr(self.proj),
                                               n.ptr(self.campos), a["tanfovx"], a["tanfovy"], 0, n.ptr(self.color),
                                               n.ptr(self.others), n.ptr(self.radii), self.debug, n.current_stream_ptr(self.dev))
+        self.rc = min(int(R), 0)      # the call's error code (0: none), kept for the tests of refused arguments
         assert R >= 0, "forward failed: %s" % n.last_error()
         self.R = int(R)
         torch.cuda.synchronize()
@@ -87,6 +88,7 @@ class HipRun:
                                                 n.ptr(g["means3D"]), None if "transMat" in skip else n.ptr(g["transMat"]),
                                                 n.ptr(g["sh"]) if M else None, n.ptr(g["scales"]),
                                                 n.ptr(g["rots"]), self.debug, n.current_stream_ptr(self.dev))
+        self.rc = int(rc)
         assert rc >= 0, "backward failed: %s" % n.last_error()
         torch.cuda.synchronize()
         return {k: v.cpu().numpy() for k, v in g.items() if k not in skip}
@@ -112,31 +114,55 @@ def check_binning(run, R, radii):
     assert np.array_equal(got, radii) and run.R <= R, (int((got != radii).sum()), run.R, R)
 
 
-def check_images(run, col, oth, st):
+def image_figures(c, o, col, oth):
+    """[(channel name, fraction of pixels within the image tolerance)] of colour [3, H, W] and the allmap [7, H, W] against a reference"""
     import determinacy as D
-    c = run.color.cpu().numpy(); o = run.others.cpu().numpy()
-    assert np.isfinite(c).all() and np.isfinite(o).all()
-    assert frac_close(c, col, D.IMG_ATOL, D.IMG_RTOL) >= D.PASS_FRAC, "color"
+    rows = [("color", frac_close(c, col, D.IMG_ATOL, D.IMG_RTOL))]
     for ch, nm in [(0, "depth-sum"), (1, "alpha"), (2, "nx"), (3, "ny"), (4, "nz"), (6, "distortion")]:
-        f = frac_close(o[ch], oth[ch], D.IMG_ATOL, D.IMG_RTOL)
-        assert f >= D.PASS_FRAC, "%s: only %.5f of pixels within tolerance" % (nm, f)
-    assert frac_close(o[5], oth[5], 1e-4, 1e-4) >= D.PASS_FRAC, "median depth"
+        rows.append((nm, frac_close(o[ch], oth[ch], D.IMG_ATOL, D.IMG_RTOL)))
+    rows.append(("median depth", frac_close(o[5], oth[5], 1e-4, 1e-4)))
+    return rows
 
 
-def check_grads(g, og, has_sr=True):
+def check_image_arrays(c, o, col, oth):
+    """check_images on host arrays (the plain-fp32 oracle's images are held to the device's bar in tests/test_inputs_cpu.py)"""
     import determinacy as D
-    pairs = [("means3D", og.dL_dmeans3D), ("opacity", og.dL_dopacity), ("sh", og.dL_dsh), ("means2D", og.dL_dmean2D)]
+    assert np.isfinite(c).all() and np.isfinite(o).all()
+    for nm, f in image_figures(c, o, col, oth):
+        assert f >= D.PASS_FRAC, "%s: only %.5f of pixels within tolerance" % (nm, f)
+
+
+def check_images(run, col, oth, st):
+    check_image_arrays(run.color.cpu().numpy(), run.others.cpu().numpy(), col, oth)
+
+
+def oracle_grads(og, has_sr=True):
+    """an oracle backward's result under the names HipRun.backward gives its gradients"""
+    g = dict(means3D=og.dL_dmeans3D, opacity=og.dL_dopacity, sh=og.dL_dsh, means2D=og.dL_dmean2D)
     if has_sr:
-        pairs += [("scales", og.dL_dscales), ("rots", og.dL_drots)]
-    for k, ref in pairs:
-        x = g[k].reshape(ref.shape)
+        g.update(scales=og.dL_dscales, rots=og.dL_drots)
+    return g
+
+
+def grad_figures(g, og, has_sr=True):
+    """[(name, fraction of elements within the gradient tolerance, surfels with an element outside it, cosine)] against the oracle"""
+    import determinacy as D
+    rows = []
+    for k, ref in oracle_grads(og, has_sr).items():
+        x = np.asarray(g[k]).reshape(ref.shape)
         assert np.isfinite(x).all(), k
         scale = np.abs(ref).mean() + 1e-30
         f = frac_close(x, ref, 1e-4 * scale + 1e-12, D.G_RTOL)
-        cs = cosine(x, ref)
+        bad = np.abs(x.astype(np.float64) - ref) > (1e-4 * scale + 1e-12 + D.G_RTOL * np.abs(ref))
+        rows.append((k, f, int(bad.reshape(bad.shape[0], -1).any(1).sum()), cosine(x, ref)))
+    return rows
+
+
+def check_grads(g, og, has_sr=True):
+    """g: gradients by HipRun.backward's names, from the device or (oracle_grads) from another run of the oracle"""
+    import determinacy as D
+    for k, f, bad_surfels, cs in grad_figures(g, og, has_sr):
         # a (pixel, surfel) pair sitting exactly on the 1/255 or 1e-4 threshold may be decided differently in fp32;
         # that moves ONE surfel's gradient, so small scenes get an absolute allowance of 3 surfels
-        bad = np.abs(x.astype(np.float64) - ref) > (1e-4 * scale + 1e-12 + D.G_RTOL * np.abs(ref))
-        bad_surfels = int(bad.reshape(bad.shape[0], -1).any(1).sum())
         assert f >= D.PASS_FRAC or bad_surfels <= 3, "%s: only %.5f of elements within tolerance, %d surfels (cos %.7f)" % (k, f, bad_surfels, cs)
         assert cs >= D.COS_MIN, "%s: cosine %.7f" % (k, cs)

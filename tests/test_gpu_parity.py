@@ -20,6 +20,7 @@ import pytest
 import determinacy as D
 from helpers import HipRun, cosine, frac_close, oracle_forward, scene_args
 from helpers import check_binning as _check_binning, check_grads as _check_grads, check_images as _check_images
+from input_cases import _stress_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -313,41 +314,6 @@ def test_precomp_and_override_color():
         scale = np.abs(ref).mean() + 1e-30
         assert frac_close(x, ref, 1e-4 * scale, G_RTOL) >= G_FRAC, k
         assert cosine(x, ref) >= G_COS, k
-
-
-def _stress_scene(kind, seed):
-    """Scenes built to break a culling rule: needle-thin, huge, grazing-angle, tiny and near-camera surfels."""
-    import synthetic
-    rng = np.random.default_rng(seed)
-    sc = synthetic.make_scene(1500, 208, 136, seed=seed, px_radius=5.0, z_near=0.6, z_far=9.0)
-    P = sc["means3D"].shape[0]
-    if kind == "needles":        # 100:1 anisotropy, every orientation
-        sc["scales"] = sc["scales"] * np.where(rng.random((P, 1)) < 0.5, [[12.0, 0.12]], [[0.1, 10.0]]).astype(np.float32)
-    elif kind == "huge":         # footprints of hundreds of pixels, some crossing the camera plane
-        sc["scales"] = sc["scales"] * rng.choice([1.0, 8.0, 40.0], size=(P, 1)).astype(np.float32)
-    elif kind == "tiny":         # sub-pixel surfels: the low-pass disc carries the whole footprint
-        sc["scales"] = sc["scales"] * rng.choice([0.02, 0.2, 1.0], size=(P, 1)).astype(np.float32)
-    elif kind == "grazing":      # discs seen almost edge-on (normal ~ perpendicular to the view ray)
-        d = sc["means3D"] - sc["campos"][None]
-        d /= np.linalg.norm(d, axis=1, keepdims=True)
-        t1 = np.cross(d, rng.normal(size=(P, 3))); t1 /= np.linalg.norm(t1, axis=1, keepdims=True)
-        n = t1 + 0.03 * rng.normal(size=(P, 1)) * d                     # normal almost perpendicular to the ray
-        n /= np.linalg.norm(n, axis=1, keepdims=True)
-        a = np.cross(n, d); a /= np.linalg.norm(a, axis=1, keepdims=True)
-        b = np.cross(n, a)
-        R = np.stack([a, b, n], 2)                                      # columns = disc axes, normal
-        R[np.linalg.det(R) < 0, :, 0] *= -1
-        w = np.sqrt(np.maximum(0, 1 + R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2])) / 2 + 1e-9
-        q = np.stack([w, (R[:, 2, 1] - R[:, 1, 2]) / (4 * w), (R[:, 0, 2] - R[:, 2, 0]) / (4 * w), (R[:, 1, 0] - R[:, 0, 1]) / (4 * w)], 1)
-        sc["rotations"] = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
-        sc["scales"] = (sc["scales"] * 3.0).astype(np.float32)
-    elif kind == "huge_faint":   # wide, nearly transparent discs close to the camera: the 3-sigma box centre runs far off screen
-        sc = synthetic.make_scene(4000, 96, 64, seed=seed, px_radius=30.0, z_near=2.0, z_far=8.0)
-        sc["opacities"] = np.full_like(sc["opacities"], 0.02)
-    elif kind == "opaque_faint":  # opacities at both ends: 1/255-ish (empty footprints) and ~1 (widest footprints)
-        sc["opacities"] = rng.choice([0.0035, 0.0045, 0.02, 0.999], size=(P, 1)).astype(np.float32)
-    sc["bg"] = np.array([0.1, 0.3, 0.7], np.float32)
-    return sc
 
 
 @pytest.mark.parametrize("kind", ["plain", "needles", "huge", "tiny", "grazing", "opaque_faint", "huge_faint"])
